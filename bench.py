@@ -2,7 +2,7 @@
 """Benchmark of the vit-tf hot path on MI355X: slices/sec of the ViT-S/8 feature-volume extraction on a 512^3 volume
 (+ the 16-query similarity step), BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,12 +14,20 @@ through ViT-S/8 (seeded synthetic weights, fp16 MFMA operands = the reference's 
 tests assert 1e-3), slice-axis pooling, the fp16 z+y+x sum (with one RCCL all-gather per axis when N > 1), then a 16-query
 similarity volume and the label volume.  Every N runs the metric's configuration: the 512^3 CT-like volume = 1536 slices
 of 512 x 512 per step (BASELINE configs[2]; sharded over the ranks for N > 1, "scaling": "strong").  value = slices pushed
-through the ViT by all ranks / wall time of the K timed steps (max over ranks).
+through the ViT by all ranks / wall time of the K timed steps (max over ranks); ms_per_step = that wall time / K.
 
-Extra objects on the JSON line: "roofline" for the kernel with the largest share of the step (durations from HIP events
-recorded on the launch stream inside the timed region, algorithmic FLOPs from SURVEY.md 8d), "roofline_similarity" for
-the similarity accumulation kernel (HBM-bound), and "cpu_baseline" (the oracle's CPU fp32 restatement of the same ViT and
-of the reference's similarity formulation on the host cores, rank 0 at N = 1, bounded samples).
+A plain run sets up, warms up, times the K steps and prints the headline line; nothing else runs on the GPU.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy in float32
+(features, similarity_ntf1, labels): an array of more than DUMP_SAMPLE elements is written as its flattened elements at
+DUMP_SAMPLE sorted indices drawn with the fixed seed DUMP_SEED (48 MB at most in all).  Inputs, weights and queries are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds, after the timed region, everything else on the same JSON line: "roofline" for the kernel with the largest
+share of the step (durations from HIP events recorded on the launch stream inside the timed region, algorithmic FLOPs
+from SURVEY.md 8d), "roofline_similarity" for the similarity accumulation kernel (HBM-bound), "roofline_block_tail",
+"roofline_gemm_qkv", "similarity", "e2e_incl_upload", BASELINE configs[3] / [4] and the fos-128 preset (N = 1, default
+configuration), and "cpu_baseline" (the oracle's CPU fp32 restatement of the same ViT and of the reference's similarity
+formulation on the host cores, rank 0 at N = 1, bounded samples).
 """
 import argparse
 import hashlib
@@ -38,13 +46,20 @@ PEAK_TFLOPS = {'bf16': 2500.0, 'fp16': 2500.0, 'fp8': 5000.0}     # dense MFMA p
 PEAK_HBM_GBS = 8000.0                              # HBM3E peak, MI355X_MICROARCH.md (6.3 TB/s achievable)
 FOS = 64
 N_QUERIES = 16
+DUMP_SAMPLE = 1 << 22                              # elements per dumped array at most (16 MB in float32)
+DUMP_SEED = 0
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=3, help='timed steps (>= 1)')
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the rooflines, the similarity leg, the upload-inclusive figure, BASELINE configs[3] / [4], '
+                         'fos 128 and the CPU baseline after the timed region (off: the headline figure only)')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='write the last timed step\'s outputs as DIR/<name>.npy (float32; seeded sample of large arrays)')
     ap.add_argument('--workload', type=str, default='512', choices=['64', '256', '512'],
                     help="512 = the metric's configuration (default for every N); 256 / 64 = BASELINE configs[1] / [0]")
     ap.add_argument('--dtype', type=str, default='fp16', choices=['fp16', 'bf16'],
@@ -55,8 +70,11 @@ def parse_args():
                     help="fp8 = BASELINE configs[3]'s fp8 MFMA attention path (informative: ~3e-2 on the features, not the contract dtype)")
     ap.add_argument('--fos', type=int, default=FOS, help='--feature-output-size (64: the metric; 128: the sub/infer_and_merge.sh preset, 1024 x 1024 slices, N = 16385)')
     ap.add_argument('--engine-batch', type=int, default=None, help='slices per engine call (default: extract.DEFAULT_ENGINE_BATCH)')
-    ap.add_argument('--cpu-slices', type=int, default=5, help='slices timed for the CPU baseline (0 = skip)')
-    return ap.parse_args()
+    ap.add_argument('--cpu-slices', type=int, default=5, help='slices timed for the CPU baseline with --full (0 = skip)')
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def spawn_ranks(args):
@@ -266,6 +284,22 @@ def cpu_baseline(sd, vol, n_slices, im_sz, arch, feats_cpu, ann, vol_shape):
     return out
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array (torch tensor on any device, or numpy) as path/<name>.npy in float32 -- whole when it has
+    at most DUMP_SAMPLE elements, else its flattened elements at DUMP_SAMPLE sorted indices drawn with seed DUMP_SEED (the
+    same indices for the same shape, run after run)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        t = torch.as_tensor(x)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, f'{name}.npy'), t.float().cpu().numpy())
+
+
 def main():
     args = parse_args()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -322,23 +356,53 @@ def main():
     def step(dvol=dvol):
         feats = vt.feature_volume(None, model, args.fos, 'all', args.engine_batch, dvol=dvol)
         sims = vt.compute_similarities(vol, feats, ann, keep_on_device=True)     # maps feed the label kernel directly
-        return feats, vt.assign_labels(sims)
+        return feats, sims, vt.assign_labels(sims)
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     barrier()
-    # HIP events around the launches of the dominant kernel only (attention, ~50 % of the kernel time): bracketing every
-    # launch costs 2-3 % of the throughput.  The other classes are timed in one extra, untimed step below.
+    # --full: HIP events around the launches of the dominant kernel only (attention, ~50 % of the kernel time): bracketing
+    # every launch costs 2-3 % of the throughput.  The other classes are timed in one extra, untimed step below.
     fullprof = os.environ.get('VITTF_BENCH_FULLPROF') == '1'
-    vt._lib.profiler_enable(True, classes=None if fullprof else ['attention'])
+    if args.full:
+        vt._lib.profiler_enable(True, classes=None if fullprof else ['attention'])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        feats, labels = step()
+        feats, sims, labels = step()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'features': feats, **{f'similarity_{k}': m for k, m in sims.items()}, 'labels': labels})
+    elapsed = max_over_ranks(elapsed)
+    out = {
+        'metric': f'slices/sec ({"ViT-S/8" if args.arch == "vits8" else "ViT-B/8"}, {args.workload}^3 vol: feature volume + '
+                  f'{N_QUERIES}-query similarity)',
+        'value': round(args.steps * total_slices / elapsed, 2),
+        'unit': 'slices/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(elapsed / args.steps * 1e3, 2), 'higher_is_better': True,
+        'scaling': 'strong', 'vs_baseline': None,      # every N runs the same 512^3 volume: total work fixed, sharded over the ranks
+        'dtype': args.dtype if args.attention == '16bit' else f'{args.dtype} (attention operands fp8 e4m3)', 'data': 'synthetic',
+        'rccl_ranks': torch.distributed.get_world_size() if world > 1 else 1,
+        'config': {'workload': desc, 'volume': list(dvol.shape), 'slices_per_step': total_slices,
+                   'image': [im_sz[0], im_sz[1]], 'tokens': n_tokens, 'feature_volume': [dim, *feat_out],
+                   'engine_batch': args.engine_batch, 'weights': f'seeded synthetic {args.arch} (seed 0)',
+                   'parallelism': f'slices sharded over {world} rank(s), one all-gather per axis' if world > 1 else 'single GPU',
+                   'dist_backend': backend},
+    }
+    if not args.full:
+        finish(out)
+        return
+
     prof = vt._lib.profiler_collect()
     if not fullprof:
         vt._lib.profiler_enable(True)                       # all classes, one step outside the timed region
@@ -349,7 +413,6 @@ def main():
             if k != 'attention':
                 prof[k] = (ms * args.steps, n * args.steps)  # scaled to the timed steps (same launches every step)
     vt._lib.profiler_enable(False)
-    elapsed = max_over_ranks(elapsed)
 
     # the reference's own bracket (infer.py:324 -> 336) also contains what bench.py's contract keeps OUT of the timed region:
     # the volume's way to the device (host fp16 -> HBM, infer.py:177 `.to(dev)`), `vol.float()` (:137) and the global
@@ -494,20 +557,7 @@ def main():
                                 '(2 D) + q, k, v out (6 D); traffic: profiles/pmc_gemm_qkv.json'}
 
     if rank == 0:
-        out = {
-            'metric': f'slices/sec ({"ViT-S/8" if args.arch == "vits8" else "ViT-B/8"}, {args.workload}^3 vol: feature volume + '
-                      f'{N_QUERIES}-query similarity)',
-            'value': round(args.steps * total_slices / elapsed, 2),
-            'unit': 'slices/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': round(elapsed / args.steps * 1e3, 2), 'higher_is_better': True,
-            'scaling': 'strong', 'vs_baseline': None,      # every N runs the same 512^3 volume: total work fixed, sharded over the ranks
-            'dtype': args.dtype if args.attention == '16bit' else f'{args.dtype} (attention operands fp8 e4m3)', 'data': 'synthetic',
-            'rccl_ranks': torch.distributed.get_world_size() if world > 1 else 1,
-            'config': {'workload': desc, 'volume': list(dvol.shape), 'slices_per_step': total_slices,
-                       'image': [im_sz[0], im_sz[1]], 'tokens': n_tokens, 'feature_volume': [dim, *feat_out],
-                       'engine_batch': args.engine_batch, 'weights': f'seeded synthetic {args.arch} (seed 0)',
-                       'parallelism': f'slices sharded over {world} rank(s), one all-gather per axis' if world > 1 else 'single GPU',
-                       'dist_backend': backend},
+        out.update({
             'roofline': roofline,
             'roofline_similarity': roofline_sim,
             'roofline_block_tail': roofline_tail,
@@ -520,7 +570,7 @@ def main():
                            'maps_bytes_to_host': int(n_classes * (dvol.shape[0] // 2) * (dvol.shape[1] // 2) * (dvol.shape[2] // 2)),
                            'note': 'ms: the reference API (uint8 maps returned as CPU tensors: ms - ms_maps_on_device is the D2H copy of '
                                    'maps_bytes_to_host over PCIe); ms_maps_on_device: keep_on_device=True'},
-        }
+        })
         out['e2e_incl_upload'] = e2e
         if (world == 1 and args.arch == 'vits8' and args.attention == '16bit' and args.fos == FOS and args.workload == '512'
                 and os.environ.get('VITTF_BENCH_EXTRAS', '1') == '1'):
@@ -529,10 +579,7 @@ def main():
             out['cpu_baseline'] = cpu_baseline(sd, vol, args.cpu_slices, im_sz, args.arch, feats.cpu(), ann, tuple(dvol.shape))
         else:
             out['cpu_baseline'] = None
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
+    finish(out)
 
 
 if __name__ == '__main__':

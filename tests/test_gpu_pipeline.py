@@ -303,6 +303,34 @@ def test_entry_points_end_to_end(gpu, tmp_path):
     assert not np.array_equal(want, want_bls), 'the solver changed nothing: the case does not tell the two paths apart'
 
 
+def test_bench_plain_run_dumps_the_last_step(gpu, tmp_path):
+    """bench.py without --full prints the headline line only; --dump-outputs writes the last timed step's arrays as float32
+    .npy within 64 MB, and two runs with the same arguments (other step counts) dump the same values: the inputs are seeded."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    dumps = []
+    for i, (steps, warmup) in enumerate(((2, 0), (1, 1))):
+        d = tmp_path / f'out{i}'
+        r = subprocess.run([sys.executable, 'bench.py', '--steps', str(steps), '--warmup', str(warmup), '--workload', '64',
+                            '--dump-outputs', str(d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr + r.stdout
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out['steps'] == steps and out['warmup'] == warmup and out['value'] > 0 and out['ms_per_step'] > 0
+        assert out['unit'] == 'slices/s' and out['higher_is_better'] is True and out['dtype'] == 'fp16'
+        slices = out['config']['slices_per_step']
+        assert abs(out['value'] * out['ms_per_step'] * 1e-3 - slices) < 1e-2 * slices
+        assert not {'roofline', 'roofline_similarity', 'similarity', 'e2e_incl_upload', 'cpu_baseline'} & set(out)
+        names = sorted(p.name for p in d.iterdir())
+        assert names == ['features.npy', 'labels.npy', 'similarity_ntf1.npy'], names
+        arrays = {n: np.load(d / n) for n in names}
+        assert all(a.dtype == np.float32 and a.size > 0 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
 def _free_port():
     import socket
     with socket.socket() as sk:
@@ -331,8 +359,8 @@ def _two_rank_checks(tmp_path, env, backend_note):
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode != 0 and 'Cache file already exists' in r.stdout, r.stderr + r.stdout
     # the benchmark's N > 1 leg (tiny workload): `python bench.py --gpus 2` starts its two ranks itself (no launcher
-    # around it) and prints its one JSON line from rank 0
-    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '1', '--warmup', '0', '--workload', '64'],
+    # around it) and prints its one JSON line from rank 0 (--full: with the roofline checked below)
+    r = subprocess.run([sys.executable, 'bench.py', '--gpus', '2', '--steps', '1', '--warmup', '0', '--workload', '64', '--full'],
                        cwd=ROOT, env={k: v for k, v in env.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')},
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr + r.stdout

@@ -207,6 +207,37 @@ def test_bench_pmc_traffic_only_for_the_measured_kernel(tmp_path, monkeypatch):
         assert bench.pmc_traffic('attention', 256, tokens=4097) == 1000
 
 
+def test_bench_options_and_seeded_inputs():
+    """A plain bench run is the headline only (--full off by default, no dump); its inputs are seeded, so two runs with the
+    same arguments see the same volume and the same query voxels."""
+    import bench
+    args = bench.parse_args([])
+    assert not args.full and args.dump_outputs is None and args.steps >= 1
+    args = bench.parse_args(['--full', '--dump-outputs', 'd', '--steps', '7'])
+    assert args.full and args.dump_outputs == 'd' and args.steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+    (v1, l1, _), (v2, l2, _) = bench.make_workload('64', vt), bench.make_workload('64', vt)
+    assert torch.equal(v1, v2) and torch.equal(l1, l2)
+    assert torch.equal(bench.query_voxels(l1)['ntf1'], bench.query_voxels(l2)['ntf1'])
+
+
+def test_bench_dump_outputs_float32_seeded_sample(tmp_path):
+    """--dump-outputs: small arrays whole (shape kept), large ones as a sorted seeded sample of DUMP_SAMPLE flat elements,
+    the same one every run; float32 only; three arrays of the flagship run stay within 64 MB."""
+    import bench
+    n = bench.DUMP_SAMPLE + 1000
+    small = np.arange(120, dtype=np.uint8).reshape(4, 5, 6)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), {'big': torch.arange(n, dtype=torch.int32), 'small': small})
+    big, small_got = np.load(tmp_path / 'a' / 'big.npy'), np.load(tmp_path / 'a' / 'small.npy')
+    assert big.dtype == small_got.dtype == np.float32
+    assert small_got.shape == small.shape and np.array_equal(small_got, small)
+    assert big.shape == (bench.DUMP_SAMPLE,) and (np.diff(big) >= 0).all() and 0 <= big.min() and big.max() < n
+    assert np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))
+    assert 3 * bench.DUMP_SAMPLE * 4 <= 64 << 20
+
+
 def test_engine_batch_follows_a_workspace_budget(monkeypatch):
     """Slices per engine call: 512 at the metric's shape (256 for models wider than 384), scaled down with the token count so
     that a call's row count stays where 512 x 4097 puts it; an explicit request or VITTF_ENGINE_BATCH wins."""
@@ -226,7 +257,14 @@ def test_engine_batch_follows_a_workspace_budget(monkeypatch):
     assert engine_batch_for(4097, 384, 32) == 8
 
 
-def test_block_tail_kernel_register_contract():
+def _kernel_asm(src, out_dir):
+    """tools/kernel_asm.sh on one source, its assembly written under out_dir (a test's own tmp_path)."""
+    env = dict(os.environ, VITTF_ASM_DIR=str(out_dir))
+    return subprocess.run(['bash', os.path.join(ROOT, 'tools', 'kernel_asm.sh'), src], capture_output=True, text=True, timeout=900,
+                          env=env)
+
+
+def test_block_tail_kernel_register_contract(tmp_path):
     """csrc/tail_fx.hip runs two waves per SIMD at exactly 256 registers with hand-counted vmcnt waits in its X waves: a spill
     reload inside a main-step loop is a vector-memory load the counts do not know of (and hipcc puts s_waitcnt vmcnt(0) in
     front of its use, which drains the weight ring), and its LDS-DMA pieces leave M0 pointing at their destination, which is
@@ -237,7 +275,7 @@ def test_block_tail_kernel_register_contract():
     if not shutil.which('/opt/rocm/bin/hipcc'):
         pytest.skip('no hipcc')
     for src, kern in (('tail_fx.hip', 'tail_fx_kernel'), ('gemm_as.hip', 'gemm_as_kernel')):
-        r = subprocess.run(['bash', os.path.join(ROOT, 'tools', 'kernel_asm.sh'), src], capture_output=True, text=True, timeout=900)
+        r = _kernel_asm(src, tmp_path)
         assert r.returncode == 0, r.stdout + r.stderr
         usage = [l for l in r.stdout.splitlines() if kern in l and 'ScratchSize' in l]
         assert len(usage) == 2, r.stdout                                       # bf16 and fp16
@@ -251,7 +289,7 @@ def test_block_tail_kernel_register_contract():
                 assert m and ('none' in m.group(1) or all(int(n) <= 16 for n in re.findall(r", (\d+)\)", m.group(1)))), l
             else:
                 assert l.rstrip().endswith('none'), l
-        asm = open('/tmp/vittf_asm/' + src.replace('.hip', '.s')).read()
+        asm = open(tmp_path / src.replace('.hip', '.s')).read()
         m0 = [l.strip() for l in asm.splitlines() if re.search(r'\bm0\b', l) and not l.strip().startswith(';')]
         ours = r's_mov_b32 (m0, s\d+|s\d+, m0)'          # lds_dma16_keep, and the prologue's lds_dma16 (saves and restores)
         assert m0 and all(re.fullmatch(ours, l) for l in m0), [l for l in m0 if not re.fullmatch(ours, l)][:5]
@@ -305,7 +343,7 @@ def _operands(ins):
     return [o.strip() for o in parts[1].split(',')] if len(parts) > 1 else []
 
 
-def test_hand_waited_registers_in_the_disassembly():
+def test_hand_waited_registers_in_the_disassembly(tmp_path):
     """Two places wait by hand for values the compiler believes are already there; both are properties of the
     generated code, so they are checked on it:
       * sim_mfma_few_kernel requests its query rows with asm loads and waits for them with a counted vmcnt behind two parts'
@@ -318,9 +356,9 @@ def test_hand_waited_registers_in_the_disassembly():
     if not shutil.which('/opt/rocm/bin/hipcc'):
         pytest.skip('no hipcc')
     for src in ('sim_mfma.hip', 'attention_fp8.hip'):
-        r = subprocess.run(['bash', os.path.join(ROOT, 'tools', 'kernel_asm.sh'), src], capture_output=True, text=True, timeout=900)
+        r = _kernel_asm(src, tmp_path)
         assert r.returncode == 0, r.stdout + r.stderr
-    few = [v for k, v in _asm_functions('/tmp/vittf_asm/sim_mfma.s').items() if 'sim_mfma_few_kernel' in k]
+    few = [v for k, v in _asm_functions(tmp_path / 'sim_mfma.s').items() if 'sim_mfma_few_kernel' in k]
     assert len(few) == 1
     ins = few[0]
     loads = [i for i, t in enumerate(ins) if t.startswith('global_load_dwordx4') and ' off' in t]
@@ -335,7 +373,7 @@ def test_hand_waited_registers_in_the_disassembly():
         assert not (touched & regs), f'{t!r} touches a query register before the counted wait'
     dma = [t for t in ins[last + 1:wait] if t.startswith(('global_load_lds', 'buffer_load')) or ' lds' in t]
     assert len(dma) == 8, f'{len(dma)} LDS-DMA pieces between the query loads and vmcnt(8)'
-    fns = {k: v for k, v in _asm_functions('/tmp/vittf_asm/attention_fp8.s').items() if 'attn_fp8_kernel' in k and 'Lb1E' in k}
+    fns = {k: v for k, v in _asm_functions(tmp_path / 'attention_fp8.s').items() if 'attn_fp8_kernel' in k and 'Lb1E' in k}
     assert len(fns) == 2
     for name, ins in fns.items():
         n_row = 0
