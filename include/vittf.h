@@ -139,6 +139,16 @@ int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit_weights* w
                          const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t qkv_part,
                          uint16_t* k_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Several thirds of the hooked qkv tensor from ONE forward (compute_qkv's return_keys=['q','k','v'], infer.py:133-135,
+ * 189-209): the forward of vittf_vit_k_features, then one projection launch for every third whose bit is set in part_mask
+ * (bit 0 = q, 1 = k, 2 = v).  Each output has vittf_vit_k_features' layout, bits, argument checks, workspace and batch
+ * limit; vittf_vit_k_features(part) is this call with part_mask = 1 << part.  The pointer of an unset bit is ignored (may
+ * be NULL); a NULL pointer for a set bit, part_mask 0 or above 7: VITTF_ERR_INVALID_ARG.
+ * [host] cfg, w, pos, view are host structs holding device pointers. */
+int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                           const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                           uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Optional timing of the launches inside vittf_vit_k_features and vittf_similarity, by kernel class, with HIP events recorded on
  * the caller's stream (what bench.py's roofline leg reads).  Process-global, off by default, not thread-safe:
  * the one exception to "no global mutable state".  enable(mask) clears earlier records and starts recording the
@@ -190,6 +200,16 @@ typedef enum vittf_epilogue {
  * `tokens` is only used by VITTF_EPI_KFEAT. */
 int vittf_gemm(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
                int32_t epilogue, int32_t tokens, int32_t dtype, void* stream);
+
+/* The VITTF_EPI_KFEAT projection for several thirds of Attention.qkv in one launch: w is the whole qkv.weight [3 d][k],
+ * bias the whole qkv.bias [3 d]; for every third p whose bit is set in part_mask (bit 0 = q, 1 = k, 2 = v) the K-feature
+ * rows of a . w[p d .. p d + d - 1]^T + bias[p d ..] go to {q,k,v}_out ([rows - CLS rows][d] fp16, the VITTF_EPI_KFEAT
+ * layout).  The grid covers the requested thirds' column tiles only, and each third is bit-equal to
+ * vittf_gemm(EPI_KFEAT) on that third's weights and bias (the same kernel, the same accumulation order).  The pointer of an
+ * unset bit is ignored (may be NULL); a NULL pointer for a set bit, part_mask 0 or above 7: VITTF_ERR_INVALID_ARG. */
+int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                           int32_t tokens, int32_t part_mask, void* q_out, void* k_out, void* v_out, int32_t dtype,
+                           void* stream);
 
 /* Residual linear + the LayerNorm that follows it:  x[rows][n] (fp32) += a[rows][k] . w[n][k]^T + bias;
  * h[rows][n] (h16) = LayerNorm(x; ln_g, ln_b, ln_eps).  Replaces attn.proj + residual + norm2 and mlp.fc2 + residual +
@@ -278,6 +298,22 @@ int vittf_pool_slices(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nsli
                       int32_t n_out, int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d,
                       uint16_t* dst, int64_t dst_stride_d, int64_t dst_stride_win, int64_t dst_stride_row,
                       int64_t dst_stride_col, void* stream);
+
+/* vittf_pool_slices with in-plane adaptive pooling too (AdaptiveAvgPool3d of any output size, infer.py:203): output
+ * voxel (i, r, c), i in [win0, win0 + nwin), r < o0 (image rows), c < o1 (image cols), is the mean over slice window i and
+ * in-plane windows r of f0 and c of f1 (adaptive rule; o0 > f0 / o1 > f1 allowed), written to
+ * dst[d*dst_stride_d + (i - win0)*dst_stride_win + r*dst_stride_row + c*dst_stride_col].  slice_dim (0, 1, 2) = the volume
+ * dimension the slices run along (x, y, z); the image rows / cols are the other two, in order.  Rounding of the CPU
+ * AdaptiveAvgPool3d on fp16: a running fp16 sum over the window in volume-dimension order (dim 0 outermost, dim 2
+ * innermost), then fp16(sum / n0), fp16(. / n1), fp16(. / n2) with the window extents along volume dims 0, 1, 2.
+ * Exception, as in torch: an output of exactly (1, 1, 1) (n_out == o0 == o1 == 1) is input.mean(), i.e. the sum over every
+ * slice accumulated in fp32 or wider, divided in fp32, rounded once to fp16 (the bits of torch's CPU mean up to its fp32
+ * summation order).
+ * Otherwise, o0 == f0 and o1 == f1 is vittf_pool_slices (the same kernel; the same bits for any slice_dim). */
+int vittf_pool_slices3d(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nslices, int32_t total_slices,
+                        int32_t n_out, int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d,
+                        uint16_t* dst, int64_t dst_stride_d, int64_t dst_stride_win, int64_t dst_stride_row,
+                        int64_t dst_stride_col, int32_t o0, int32_t o1, int32_t slice_dim, void* stream);
 
 /* out = fp16(fp16(z + y) + x) element-wise: the reference's running fp16 sum in z, y, x order
  * (infer.py:330-332).  Inputs are the per-axis pooled volumes as gathered from `nranks` ranks:

@@ -139,18 +139,24 @@ def compute_qkv(vol, model, patch_size, im_sizes, pool_fn=_noop, batch_size=1, s
         raise ValueError(f'patch_size {patch_size} != model patch size {model.patch_size}')
     dvol = vt.DeviceVolume(vol, model.device)
     eb = vt.extract.AtLeast(batch_size) if int(batch_size) > 1 else None      # a lower bound: the engine sizes its own calls
+    # every requested third from ONE engine forward per slice batch (the reference's single hook, :133-135, 189-209)
+    parts = sorted({vt.extract.PARTS[key] for key in return_keys})
+    if not parts:
+        return {}
+    if isinstance(pool_fn, torch.nn.AdaptiveAvgPool3d):
+        size = pool_fn.output_size
+        size = (size,) * 3 if isinstance(size, int) or size is None else tuple(size)
+        res = vt.pooled_axis(None, model, slice_along, tuple(im_sizes), size, eb, group=group, dvol=dvol, parts=parts)
+    else:
+        sl = vt.AXIS_DIMS[slice_along][0]
+        g, _ = vt.extract.axis_features(model, dvol, slice_along, tuple(im_sizes), dvol.shape[sl], eb, group=group,
+                                        parts=parts)
+        full = vt.extract.assemble_axis(g, slice_along, dvol.shape[sl])
+        d = model.embed_dim
+        res = {p: pool_fn(full[i * d:(i + 1) * d]) for i, p in enumerate(parts)}
     out = {}
     for key in return_keys:
-        part = vt.extract.PARTS[key]
-        if isinstance(pool_fn, torch.nn.AdaptiveAvgPool3d):
-            size = pool_fn.output_size
-            size = (size,) * 3 if isinstance(size, int) else tuple(size)
-            res = vt.pooled_axis(None, model, slice_along, tuple(im_sizes), size, eb, part, group, dvol)
-        else:
-            sl = vt.AXIS_DIMS[slice_along][0]
-            g, _ = vt.extract.axis_features(model, dvol, slice_along, tuple(im_sizes), dvol.shape[sl], eb, part, group)
-            res = pool_fn(vt.extract.assemble_axis(g, slice_along, dvol.shape[sl]))
-        out[key] = res.cpu()
+        out[key] = res[vt.extract.PARTS[key]].cpu()
     return out
 
 

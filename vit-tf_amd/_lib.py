@@ -62,12 +62,15 @@ SIGNATURES = {
     'vittf_vit_workspace_bytes': (_sz, [_P(VitConfig), _i32, _i32]),
     'vittf_vit_k_features': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
                                        _vp, _vp, _sz, _vp]),
+    'vittf_vit_qkv_features': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
+                                         _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_profiler_enable': (C.c_int, [_i32]),
     'vittf_profiler_collect': (C.c_int, [_P(C.c_double), _P(_i64)]),
     'vittf_profiler_kernel_name': (C.c_char_p, [_i32]),
     'vittf_patch_embed': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _vp, _vp]),
     'vittf_layernorm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, _vp]),
     'vittf_gemm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    'vittf_gemm_kfeat_parts': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     'vittf_gemm_residual_ln': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp]),
     'vittf_block_tail_workspace_bytes': (_sz, []),
     'vittf_block_tail': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _vp]),
@@ -81,6 +84,8 @@ SIGNATURES = {
     'vittf_attention_fp8_rows': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     'vittf_pool_slices': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64,
                                     _i64, _vp]),
+    'vittf_pool_slices3d': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i64,
+                                      _i64, _i32, _i32, _i32, _vp]),
     'vittf_assemble_sum': (C.c_int, [_vp, _vp, _vp, _i32, _P(_i32), _i32, _i32, _i32, _i32, _vp, _vp]),
     'vittf_sample_features': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     'vittf_voxel_norm': (C.c_int, [_vp, _i32, _i64, _vp, _vp]),

@@ -2,8 +2,8 @@
 //
 // Replaces the body of the reference's hot loop `model(F.interpolate(im_in[batch], ...).to(dev))` plus the
 // forward hook on blocks[-1].attn.qkv (infer.py:133-135, 173-177): patch embed, (L-1) full pre-norm blocks and
-// then only LayerNorm1 + the K third of the last block's qkv projection -- the rest of block L and the final
-// norm never influence the hooked tensor, so they are not executed.
+// then only LayerNorm1 + the requested thirds (q, k, v) of the last block's qkv projection, in one launch -- the rest
+// of block L and the final norm never influence the hooked tensor, so they are not executed.
 //
 // Workspace layout for `batch` slices of N tokens (rows = batch * N, padded to the GEMM tile):
 //   X    fp32 [rows][D]      residual stream
@@ -103,11 +103,13 @@ extern "C" size_t vittf_vit_workspace_bytes(const vittf_vit_config* cfg, int32_t
                    cfg->attention_fp8 ? vittf_attention_fp8_workspace_bytes(batch, tokens, cfg->heads) : 0).total;
 }
 
-extern "C" int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
-                                    const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t qkv_part,
-                                    uint16_t* k_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!config_ok(cfg) || !w || !pos || !view || !k_out || !ws || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
-  if (qkv_part < 0 || qkv_part > 2) return VITTF_ERR_INVALID_ARG;
+extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                      const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                      uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  if (!config_ok(cfg) || !w || !pos || !view || !ws || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
+  if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
+  if (((part_mask & 1) && !q_out) || ((part_mask & 2) && !k_out) || ((part_mask & 4) && !v_out)) return VITTF_ERR_INVALID_ARG;
   if (!w->qkv_w || !w->qkv_b || !w->proj_w || !w->proj_b || !w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b ||
       !w->ln1_g || !w->ln1_b || !w->ln2_g || !w->ln2_b)
     return VITTF_ERR_INVALID_ARG;
@@ -153,11 +155,10 @@ extern "C" int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit
       if (rc) return rc;
     }
     if (l == L - 1) {
-      // hooked tensor, one third only: rows [part*D, (part+1)*D) of qkv.weight / qkv.bias  (infer.py:189-201)
-      ProfScope ps(VITTF_KERNEL_GEMM, stream);   // the K-feature projection (tiled kernel)
-      return vittf_gemm(H, qkv_w + (size_t)qkv_part * d * d * esz, w->qkv_b + (size_t)l * 3 * d + (size_t)qkv_part * d,
-                        k_out, rows, d, d,
-                        VITTF_EPI_KFEAT, tokens, dt, stream);
+      // hooked tensor, the requested thirds only: rows [part*D, (part+1)*D) of qkv.weight / qkv.bias  (infer.py:189-209)
+      ProfScope ps(VITTF_KERNEL_GEMM, stream);   // the K-feature projection: one launch for every requested third
+      return vittf_gemm_kfeat_parts(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, rows, d, d, tokens, part_mask, q_out, k_out, v_out,
+                                    dt, stream);
     }
     { ProfScope ps(VITTF_KERNEL_GEMM_QKV, stream);
       if (fp8_rows)
@@ -217,6 +218,17 @@ extern "C" int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit
     if (rc) return rc;
   }
   return VITTF_OK;
+}
+
+// one third: the same forward with a one-bit mask (the bytes of the single-third projection)
+extern "C" int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                    const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t qkv_part,
+                                    uint16_t* k_out, void* ws, size_t ws_bytes, void* stream) {
+  if (!k_out || qkv_part < 0 || qkv_part > 2) return VITTF_ERR_INVALID_ARG;
+  uint16_t* outs[3] = {nullptr, nullptr, nullptr};
+  outs[qkv_part] = k_out;
+  return vittf_vit_qkv_features(cfg, w, pos, view, slice0, batch, 1 << qkv_part, outs[0], outs[1], outs[2], ws, ws_bytes,
+                                stream);
 }
 
 static const char* g_kernel_names[VITTF_KERNEL_CLASSES] = {};

@@ -40,12 +40,23 @@ __device__ __forceinline__ void stage_tile(const T* __restrict__ src, int64_t ld
   for (int i = 0; i < 4; ++i) lds_dma16(rsrc, lds_tile + i * 4096, voff[i], k0 * 2);
 }
 
+// Several thirds of attn.qkv in one launch (vittf_gemm_kfeat_parts): W / bias are the whole [n = 3 d][k] / [3 d] of the
+// projection and the grid covers only the column tiles of the requested thirds, slot s of them = third part[s]; each third
+// leaves with the K-feature epilogue into its own [rows - CLS rows][d] output.  A tile reads the same weight rows and bias
+// as the single-third launch on that third's weights: the same bits.
+constexpr int EPI_KFEAT_PARTS = 100;      // (internal epilogue id)
+struct KfeatParts {
+  unsigned short* out[3];   // by third (q, k, v)
+  int part[3];              // slot -> third
+  int d;
+};
+
 template <int DT, int EPI, int NSTAGE>
 __global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const unsigned short* __restrict__ A,
                                                       const unsigned short* __restrict__ W,
                                                       const float* __restrict__ bias, void* __restrict__ out,
                                                       int64_t rows, int n, int k, int tokens, int n_tiles,
-                                                      int total_tiles) {
+                                                      int total_tiles, KfeatParts kp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][A tile | W tile]
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -55,7 +66,15 @@ __global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const un
   const int tile = xcd_remap(blockIdx.x, total_tiles);
   const int mt = tile / n_tiles, nt = tile - mt * n_tiles;
   const int64_t m0 = (int64_t)mt * BM;
-  const int n0 = nt * BN;
+  int n0 = nt * BN;
+  [[maybe_unused]] unsigned short* part_out = nullptr;   // (EPI_KFEAT_PARTS) this tile's third: output, first column
+  [[maybe_unused]] int part_col0 = 0;
+  if constexpr (EPI == EPI_KFEAT_PARTS) {
+    const int slot = n0 / kp.d;
+    part_col0 = n0 - slot * kp.d;
+    n0 = kp.part[slot] * kp.d + part_col0;
+    part_out = kp.out[kp.part[slot]];
+  }
 
   f32x16_t acc[2][2];  // [ni][mi]
 #pragma unroll
@@ -187,7 +206,7 @@ __global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const un
             v0 *= sc; v1 *= sc; v2 *= sc; v3 *= sc;
           }
           uint2 pk;
-          if constexpr (EPI == VITTF_EPI_KFEAT) {
+          if constexpr (EPI == VITTF_EPI_KFEAT || EPI == EPI_KFEAT_PARTS) {
             pk.x = pack2_h16<VITTF_FP16>(v0, v1);
             pk.y = pack2_h16<VITTF_FP16>(v2, v3);
           } else {
@@ -206,22 +225,26 @@ __global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const un
       const int64_t m = m0 + rl;
       if (m >= rows) continue;
       int64_t orow = m;
-      if constexpr (EPI == VITTF_EPI_KFEAT) {
+      if constexpr (EPI == VITTF_EPI_KFEAT || EPI == EPI_KFEAT_PARTS) {
         const int64_t b = m / tokens;
         const int tok = (int)(m - b * tokens);
         if (tok == 0) continue;  // CLS row dropped (infer.py:202 k[:, 1:])
         orow = b * (tokens - 1) + tok - 1;
       }
       const uint4 v = *reinterpret_cast<const uint4*>(smem + rl * CS + (tid & 15) * 16);
-      *reinterpret_cast<uint4*>(o16 + orow * n + n0 + (tid & 15) * 8) = v;
+      if constexpr (EPI == EPI_KFEAT_PARTS)
+        *reinterpret_cast<uint4*>(part_out + orow * kp.d + part_col0 + (tid & 15) * 8) = v;
+      else
+        *reinterpret_cast<uint4*>(o16 + orow * n + n0 + (tid & 15) * 8) = v;
     }
   }
 }
 
 template <int DT>
 int launch_gemm(const void* a, const void* w, const float* bias, void* out, int64_t rows, int n, int k, int epi,
-                int tokens, hipStream_t st) {
-  const int m_tiles = (int)((rows + BM - 1) / BM), n_tiles = n / BN;
+                int tokens, hipStream_t st, KfeatParts kp = KfeatParts{}, int part_tiles = 0) {
+  // (EPI_KFEAT_PARTS: n = 3 d weight rows, part_tiles = the requested thirds' column tiles)
+  const int m_tiles = (int)((rows + BM - 1) / BM), n_tiles = epi == EPI_KFEAT_PARTS ? part_tiles : n / BN;
   const int total = m_tiles * n_tiles;
   // 1 = one 32 KB operand stage and four workgroups per CU (default: +16 % on the K = 384 shapes, whose six
   // K steps are too short for a two-stage pipeline to cover the load latency); 2 = double buffer, two per CU
@@ -239,10 +262,10 @@ int launch_gemm(const void* a, const void* w, const float* bias, void* out, int6
     }                                                                                                        \
     if (nstage == 1)                                                                                         \
       hipLaunchKernelGGL((gemm_kernel<DT, E, 1>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k, \
-                         tokens, n_tiles, total);                                                            \
+                         tokens, n_tiles, total, kp);                                                        \
     else                                                                                                     \
       hipLaunchKernelGGL((gemm_kernel<DT, E, 2>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k, \
-                         tokens, n_tiles, total);                                                            \
+                         tokens, n_tiles, total, kp);                                                        \
     break;                                                                                                   \
   }
   switch (epi) {
@@ -251,6 +274,7 @@ int launch_gemm(const void* a, const void* w, const float* bias, void* out, int6
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_RESIDUAL)
     VITTF_GEMM_CASE(VITTF_EPI_KFEAT)
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_QKV)
+    VITTF_GEMM_CASE(EPI_KFEAT_PARTS)
     default: return VITTF_ERR_INVALID_ARG;
   }
 #undef VITTF_GEMM_CASE
@@ -264,6 +288,10 @@ int vittf_gemm_rows(const void* a, const void* w, const float* bias, float* x, i
 
 int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
                   int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st);   // gemm_pp.hip; 1 = not covered
+
+int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                              int32_t tokens, int32_t part_mask, void* const outs[3], int32_t dtype, hipStream_t st,
+                              int32_t* taken);   // gemm_pp.hip
 
 // K >= 768 with N % 256 == 0 (the ViT-B linears) run on the persistent 256 x 256 kernel of gemm_pp.hip.  Residual linears with
 // 768 output columns take it from K = 3072 on (fc2: the LayerNorm behind it then runs as its own launch instead of in the
@@ -290,6 +318,41 @@ extern "C" int vittf_gemm(const void* a, const void* w, const float* bias, void*
   if (dtype == VITTF_BF16) return launch_gemm<VITTF_BF16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
   if (dtype == VITTF_FP16) return launch_gemm<VITTF_FP16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
   return VITTF_ERR_INVALID_ARG;
+}
+
+// The thirds of attn.qkv selected by part_mask (bit 0 q, 1 k, 2 v) in one launch per kernel, each with the K-feature epilogue
+// into its own output.  Every third runs on the kernel its own vittf_gemm(EPI_KFEAT) call would take -- the persistent
+// 256 x 256 kernel where it covers the shape, alignment and output size, else the 128 x 128 tiles --, so its bits are that
+// call's.
+extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                                      int32_t tokens, int32_t part_mask, void* q_out, void* k_out, void* v_out, int32_t dtype,
+                                      void* stream) {
+  void* const outs[3] = {q_out, k_out, v_out};
+  if (!a || !w || !bias || rows <= 0 || d <= 0 || k <= 0 || tokens < 2) return VITTF_ERR_INVALID_ARG;
+  if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
+  for (int p = 0; p < 3; ++p)
+    if (((part_mask >> p) & 1) && !outs[p]) return VITTF_ERR_INVALID_ARG;
+  if (d % BN != 0 || k % BK != 0) return VITTF_ERR_INVALID_ARG;
+  if (rows / BM + 1 > (1 << 20)) return VITTF_ERR_INVALID_ARG;
+  if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t taken = 0;
+  const int rc = vittf_gemm_pp_kfeat_parts(a, w, bias, rows, d, k, tokens, part_mask, outs, dtype, st, &taken);
+  if (rc != VITTF_OK) return rc;
+  const int rest = part_mask & ~taken;
+  if (!rest) return VITTF_OK;
+  KfeatParts kp{};
+  int slots = 0;
+  for (int p = 0; p < 3; ++p) {
+    kp.out[p] = (unsigned short*)outs[p];
+    if ((rest >> p) & 1) kp.part[slots++] = p;
+  }
+  kp.d = d;
+  const int part_tiles = slots * (d / BN);
+  vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_kernel");   // (the projection is the engine's last launch: its class name tells which ran)
+  if (dtype == VITTF_BF16)
+    return launch_gemm<VITTF_BF16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
+  return launch_gemm<VITTF_FP16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
 }
 
 // x += a . w^T + bias (fp32 residual stream, n = 384), then h = LayerNorm(x; g, b) as the 16-bit operand of the next

@@ -84,13 +84,26 @@ __device__ __forceinline__ int pp_scale_exp(float amax) {
   return ex < -20 ? -20 : ex;
 }
 
+// Several thirds of attn.qkv in one launch with the K-feature epilogue (entry point vittf_gemm_pp_kfeat_parts below; internal
+// epilogue id): W / bias are the whole projection, the grid covers the column tiles of the requested thirds only (slot s =
+// third part[s]), and each third leaves through a descriptor of its own over its own output (64-bit base, `bytes` long).
+// Dropped rows (CLS, rows past the end) are predicated off, not sent to an out-of-range offset; the tile's stores are then
+// fewer than the counted waits of the next tile's first stages assume, so this epilogue ends on a full vmcnt(0).
+constexpr int PP_EPI_KFEAT_PARTS = 101;
+struct PpParts {
+  char* out[3];             // by third (q, k, v)
+  int part[3];              // slot -> third
+  int d;
+  unsigned bytes;           // of each output
+};
+
 struct Frags { s16x8_t a[4][2], w[2][2]; };      // [32-row block][k16 step]
 
 template <int DT, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* __restrict__ A, const unsigned short* __restrict__ W,
                                                          const float* __restrict__ bias, void* __restrict__ out, int64_t rows,
                                                          int n, int k, int tokens, int n_tiles, int total_tiles,
-                                                         unsigned out_bytes, PpFp8Out f8) {
+                                                         unsigned out_bytes, PpFp8Out f8, PpParts kp) {
   __shared__ __attribute__((aligned(16))) char smem[PLDS];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -123,6 +136,10 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
     const int mt = tile / n_tiles;
     m0 = (int64_t)mt * PBM;
     n0 = (tile - mt * n_tiles) * PBN;
+    if constexpr (EPI == PP_EPI_KFEAT_PARTS) {     // slot column -> column of the whole projection (weight row, bias)
+      const int slot = n0 / kp.d;
+      n0 = kp.part[slot] * kp.d + (n0 - slot * kp.d);
+    }
   };
   auto d_open = [&](int vb) {
     int64_t m0; int n0;
@@ -391,7 +408,19 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
               if constexpr (EPI == VITTF_EPI_BIAS_QKV) v[e] *= qs;   // the q third: softmax scale and exp -> exp2 base change
             }
             pu32x4_t pk;
-            if constexpr (EPI == VITTF_EPI_KFEAT) {
+            if constexpr (EPI == PP_EPI_KFEAT_PARTS) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
+              const int third = n0 / kp.d;
+              const auto rp = __builtin_amdgcn_make_buffer_rsrc(kp.out[third], 0, (int)kp.bytes, 0x00020000);
+              const int64_t m = row0 + rl;
+              const int64_t b = m / tokens;
+              const int tok = (int)(m - b * tokens);
+              const int64_t orow = b * (tokens - 1) + tok - 1;
+              if (m < rows && tok != 0)        // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
+                __builtin_amdgcn_raw_buffer_store_b128(pk, rp, (int)(unsigned)((orow * kp.d + (n0 - third * kp.d) + 4 * ch) * 2),
+                                                       0, PV_ST_AUX);
+            } else if constexpr (EPI == VITTF_EPI_KFEAT) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
               const int64_t m = row0 + rl;
@@ -409,6 +438,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
         }
         PP_BARRIER();
       }
+      if constexpr (EPI == PP_EPI_KFEAT_PARTS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (predicated stores: see PpParts)
       if constexpr (EPI == PP_EPI_QKV_FP8) {
         const int dm = n / 3;
         if (n0 / dm == 2) {
@@ -433,9 +463,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
 
 template <int DT>
 int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int n, int k, int epi, int tokens,
-              hipStream_t st, PpFp8Out f8 = PpFp8Out{}) {
+              hipStream_t st, PpFp8Out f8 = PpFp8Out{}, PpParts kp = PpParts{}, int part_tiles = 0) {
   const int64_t m_tiles = (rows + PBM - 1) / PBM;
-  const int n_tiles = n / PBN;
+  const int n_tiles = epi == PP_EPI_KFEAT_PARTS ? part_tiles : n / PBN;
   const int64_t total64 = m_tiles * n_tiles;
   if (total64 > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
   const int total = (int)total64;
@@ -454,7 +484,7 @@ int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_
 #define VITTF_PP_CASE(E)                                                                                              \
   case E:                                                                                                             \
     hipLaunchKernelGGL((gemm_pp_kernel<DT, E>), dim3(grid), dim3(512), 0, st, A, Wp, bias, out, rows, n, k, tokens,   \
-                       n_tiles, total, out_bytes, f8);                                                                \
+                       n_tiles, total, out_bytes, f8, kp);                                                            \
     break;
   switch (epi) {
     VITTF_PP_CASE(VITTF_EPI_BIAS)
@@ -463,6 +493,7 @@ int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_
     VITTF_PP_CASE(VITTF_EPI_KFEAT)
     VITTF_PP_CASE(VITTF_EPI_BIAS_QKV)
     VITTF_PP_CASE(PP_EPI_QKV_FP8)
+    VITTF_PP_CASE(PP_EPI_KFEAT_PARTS)
     default: return VITTF_ERR_INVALID_ARG;
   }
 #undef VITTF_PP_CASE
@@ -488,6 +519,36 @@ int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, in
   if (dtype == VITTF_BF16) return launch_pp<VITTF_BF16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
   if (dtype == VITTF_FP16) return launch_pp<VITTF_FP16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
   return VITTF_ERR_INVALID_ARG;
+}
+
+// vittf_gemm_kfeat_parts' persistent leg: the thirds of part_mask whose single-third vittf_gemm(EPI_KFEAT) call would run here
+// (same shape, alignment and output-size rules as vittf_gemm_pp + launch_pp; on [3 d][k] weights, a third's are 16-byte
+// aligned when the whole are) in one launch.  *taken = the thirds launched; the others are the caller's.
+int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                              int32_t tokens, int32_t part_mask, void* const outs[3], int32_t dtype, hipStream_t st,
+                              int32_t* taken) {
+  *taken = 0;
+  if (k < 768 || k % (2 * PBK) != 0 || d % PBN != 0) return VITTF_OK;
+  if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)d * 4 * 64 > 0x7fffffff) return VITTF_OK;
+  if ((((uintptr_t)a | (uintptr_t)w) & 15) != 0) return VITTF_OK;
+  const int64_t ob = (rows - rows / tokens) * (int64_t)d * 2;
+  if (ob > 0xfffffff0ll) return VITTF_OK;
+  PpParts kp{};
+  int slots = 0, mask = 0;
+  for (int p = 0; p < 3; ++p) {
+    kp.out[p] = (char*)outs[p];
+    if (((part_mask >> p) & 1) && ((uintptr_t)outs[p] & 15) == 0) { kp.part[slots++] = p; mask |= 1 << p; }
+  }
+  if (!mask) return VITTF_OK;
+  kp.d = d;
+  kp.bytes = (unsigned)ob;
+  vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_pp_kernel");
+  const int part_tiles = slots * (d / PBN);
+  const int rc = dtype == VITTF_BF16
+      ? launch_pp<VITTF_BF16>(a, w, bias, outs[kp.part[0]], rows, d, k, PP_EPI_KFEAT_PARTS, tokens, st, PpFp8Out{}, kp, part_tiles)
+      : launch_pp<VITTF_FP16>(a, w, bias, outs[kp.part[0]], rows, d, k, PP_EPI_KFEAT_PARTS, tokens, st, PpFp8Out{}, kp, part_tiles);
+  if (rc == VITTF_OK) *taken = mask;
+  return rc;
 }
 
 #ifndef PP_STANDALONE

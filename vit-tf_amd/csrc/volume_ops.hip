@@ -2,10 +2,13 @@
 // fp16 z + y + x sum over the per-axis pooled volumes gathered from all ranks.
 //
 // Replaces k[:, 1:].view(S, f0, f1, D).permute(0, 3, 1, 2).permute(permute_out) (infer.py:201-203),
-// torch.nn.AdaptiveAvgPool3d(feat_out_sz) (infer.py:329; in-plane it is the identity because the token grid
-// already equals feat_out_sz, only the slice axis is reduced) and the running fp16 sum of infer.py:330-332.
+// torch.nn.AdaptiveAvgPool3d(size) (infer.py:203, :329: any output size; for the driver's feat_out_sz the token grid
+// already equals the in-plane size, so in-plane windows are one token wide and only the slice axis is reduced) and the
+// running fp16 sum of infer.py:330-332.
 // Rounding follows the reference's CPU path bit for bit: the CPU kernel of AdaptiveAvgPool3d accumulates a
-// window in the tensor dtype (fp16, one rounding per add, slice order) and rounds sum / count once more.
+// window in the tensor dtype (fp16, one rounding per add) in volume-dimension order (dim 0 outermost, dim 2 innermost),
+// then divides by the window's extent along volume dims 0, 1 and 2 in turn, rounding to fp16 after each division.
+// One-token-wide in-plane windows make that the slice-order sum and ONE rounding of sum / count (dividing by 1 is exact).
 // HBM-bound byte shuffling: 16-byte loads along the feature dim, an LDS transpose, 128-byte store runs.
 #include "vittf_common.h"
 
@@ -18,12 +21,18 @@ __device__ __forceinline__ float f16_round(float v) { return f16bits_to_f32(f32_
 struct PoolArgs {
   const unsigned short* k;
   int k_slice0, k_nslices, total_slices, n_out, win0, nwin, f0, f1, d;
+  int o0, o1;       // in-plane output sizes (image rows, cols)
+  int slice_dim;    // volume dim of the slices: the rows / cols are the other two, in order
   unsigned short* dst;
   int64_t sd, sw, sr, sc;
   int fast_is_win;  // 1: the window index is the contiguous output dim, 0: the token column is
   int tiles_fast;   // tiles along the fast dim
 };
 
+// IN_PLANE = false: the in-plane output is the token grid (o0 == f0, o1 == f1), so a window is one slice column: the
+// instantiation vittf_pool_slices launches, without the in-plane window arithmetic (the general loop nest measured 11 %
+// slower at the benchmark's shape, 0.395 -> 0.437 ms per launch).  Both give the same bits there.
+template <bool IN_PLANE>
 __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
   __shared__ unsigned short tile[PT][PT + 2];
   const int tid = threadIdx.x;
@@ -34,13 +43,13 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
   const int ft = bid % a.tiles_fast; bid /= a.tiles_fast;
   int row, col0, win0, n_items;
   if (a.fast_is_win) {        // outer = (row, col), items = windows
-    col0 = bid % a.f1; row = bid / a.f1;
+    col0 = bid % a.o1; row = bid / a.o1;
     win0 = ft * PT;
     n_items = min(PT, a.nwin - win0);
   } else {                    // outer = (row, window), items = columns
     win0 = bid % a.nwin; row = bid / a.nwin;
     col0 = ft * PT;
-    n_items = min(PT, a.f1 - col0);
+    n_items = min(PT, a.o1 - col0);
   }
   const int d0 = dt * PT;
 
@@ -52,13 +61,10 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
     if (item < n_items) {
       const int w = a.win0 + (a.fast_is_win ? win0 + item : win0);
       const int col = a.fast_is_win ? col0 : col0 + item;
-      const int lo = (int)(((int64_t)w * a.total_slices) / a.n_out);
-      const int hi = (int)((((int64_t)(w + 1)) * a.total_slices + a.n_out - 1) / a.n_out);
       float acc[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-      for (int s = lo; s < hi; ++s) {
-        const int64_t off = (((int64_t)(s - a.k_slice0) * a.f0 + row) * a.f1 + col) * a.d + d0 + dl;
+      auto add8 = [&](int64_t off) {
         const uint4 raw = *reinterpret_cast<const uint4*>(a.k + off);
         const unsigned u[4] = {raw.x, raw.y, raw.z, raw.w};
 #pragma unroll
@@ -67,10 +73,36 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
           acc[2 * j] = f16_round(acc[2 * j] + f16bits_to_f32((unsigned short)(u[j] & 0xffff)));
           acc[2 * j + 1] = f16_round(acc[2 * j + 1] + f16bits_to_f32((unsigned short)(u[j] >> 16)));
         }
-      }
-      const float cnt = (float)(hi - lo);
+      };
+      if constexpr (!IN_PLANE) {
+        const int lo = (int)(((int64_t)w * a.total_slices) / a.n_out);
+        const int hi = (int)((((int64_t)(w + 1)) * a.total_slices + a.n_out - 1) / a.n_out);
+        for (int s = lo; s < hi; ++s) add8((((int64_t)(s - a.k_slice0) * a.f0 + row) * a.f1 + col) * a.d + d0 + dl);
+        const float cnt = (float)(hi - lo);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) tile[item][dl + j] = f32_to_f16bits(acc[j] / cnt);
+        for (int j = 0; j < 8; ++j) tile[item][dl + j] = f32_to_f16bits(acc[j] / cnt);
+      } else {
+        // the window along (slices, rows, cols) and the element stride of each in the token-major slices
+        const int sl = a.slice_dim, dr = sl == 0 ? 1 : 0, dc = sl == 2 ? 1 : 2;     // volume dims of slices, rows, cols
+        int lo[3], hi[3];
+        int64_t st[3];
+        lo[sl] = (int)(((int64_t)w * a.total_slices) / a.n_out);
+        hi[sl] = (int)((((int64_t)(w + 1)) * a.total_slices + a.n_out - 1) / a.n_out);
+        st[sl] = (int64_t)a.f0 * a.f1 * a.d;
+        lo[dr] = (int)(((int64_t)row * a.f0) / a.o0);
+        hi[dr] = (int)((((int64_t)(row + 1)) * a.f0 + a.o0 - 1) / a.o0);
+        st[dr] = (int64_t)a.f1 * a.d;
+        lo[dc] = (int)(((int64_t)col * a.f1) / a.o1);
+        hi[dc] = (int)((((int64_t)(col + 1)) * a.f1 + a.o1 - 1) / a.o1);
+        st[dc] = a.d;
+        const int64_t base = d0 + dl - (int64_t)a.k_slice0 * st[sl];
+        for (int i0 = lo[0]; i0 < hi[0]; ++i0)
+          for (int i1 = lo[1]; i1 < hi[1]; ++i1)
+            for (int i2 = lo[2]; i2 < hi[2]; ++i2) add8(base + i0 * st[0] + i1 * st[1] + i2 * st[2]);
+        const float n0 = (float)(hi[0] - lo[0]), n1 = (float)(hi[1] - lo[1]), n2 = (float)(hi[2] - lo[2]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) tile[item][dl + j] = f32_to_f16bits(f16_round(f16_round(acc[j] / n0) / n1) / n2);
+      }
     }
   }
   __syncthreads();
@@ -87,6 +119,40 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
       a.dst[(int64_t)(d0 + dl) * a.sd + base] = tile[item][dl];
     }
   }
+}
+
+// AdaptiveAvgPool3d to exactly (1, 1, 1): torch does not pool there, it returns input.mean(), which for fp16 on the CPU is
+// an fp32 sum, an fp32 division by the voxel count and one rounding to fp16 -- the true mean, where the running fp16 sum of
+// pool_kernel would stall (or overflow) over a whole axis.  Here: an fp64 sum per feature (a thread's rows, then a fixed-order
+// tree over the 256 threads: deterministic), rounded to fp32, divided in fp32, rounded to fp16; the bits of torch's fp32 sum
+// up to its own summation order.  One workgroup per 8 features; rows [row0, row0 + nrows) of [rows][d] token-major slices.
+__global__ __launch_bounds__(256) void mean_all_kernel(const unsigned short* __restrict__ k, int64_t row0, int64_t nrows, int d,
+                                                       unsigned short* __restrict__ dst, int64_t sd) {
+  __shared__ double part[256][9];
+  const int tid = threadIdx.x, f0 = blockIdx.x * 8;
+  double acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+  for (int64_t r = tid; r < nrows; r += 256) {
+    const uint4 raw = *reinterpret_cast<const uint4*>(k + (row0 + r) * d + f0);
+    const unsigned u[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[2 * j] += (double)f16bits_to_f32((unsigned short)(u[j] & 0xffff));
+      acc[2 * j + 1] += (double)f16bits_to_f32((unsigned short)(u[j] >> 16));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[tid][j] = acc[j];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) part[tid][j] += part[tid + w][j];
+    }
+    __syncthreads();
+  }
+  if (tid < 8) dst[(int64_t)(f0 + tid) * sd] = f32_to_f16bits((float)part[0][tid] / (float)nrows);
 }
 
 __global__ __launch_bounds__(256) void assemble_sum_kernel(const unsigned short* __restrict__ gz,
@@ -212,13 +278,16 @@ __global__ __launch_bounds__(256) void widen_f16_kernel(const unsigned short* __
 
 }  // namespace
 
-extern "C" int vittf_pool_slices(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nslices, int32_t total_slices,
-                                 int32_t n_out, int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d,
-                                 uint16_t* dst, int64_t dst_stride_d, int64_t dst_stride_win, int64_t dst_stride_row,
-                                 int64_t dst_stride_col, void* stream) {
+// global_mean: an output of exactly (1, 1, 1) is torch's input.mean() (mean_all_kernel) -- vittf_pool_slices3d; vittf_pool_slices
+// keeps the pooling rule there (the ABI 6 behaviour of its callers)
+static int pool_slices(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nslices, int32_t total_slices, int32_t n_out,
+                       int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d, uint16_t* dst, int64_t dst_stride_d,
+                       int64_t dst_stride_win, int64_t dst_stride_row, int64_t dst_stride_col, int32_t o0, int32_t o1,
+                       int32_t slice_dim, bool global_mean, void* stream) {
   if (!k_slices || !dst || total_slices <= 0 || n_out <= 0 || nwin <= 0 || win0 < 0 || win0 + nwin > n_out)
     return VITTF_ERR_INVALID_ARG;
   if (f0 <= 0 || f1 <= 0 || d <= 0 || d % PT != 0 || k_nslices <= 0 || k_slice0 < 0) return VITTF_ERR_INVALID_ARG;
+  if (o0 <= 0 || o1 <= 0 || slice_dim < 0 || slice_dim > 2) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)k_slices & 15) != 0) return VITTF_ERR_INVALID_ARG;
   // every slice touched by the requested windows must be resident
   const int64_t lo = ((int64_t)win0 * total_slices) / n_out;
@@ -227,14 +296,39 @@ extern "C" int vittf_pool_slices(const uint16_t* k_slices, int32_t k_slice0, int
   PoolArgs a;
   a.k = k_slices; a.k_slice0 = k_slice0; a.k_nslices = k_nslices; a.total_slices = total_slices; a.n_out = n_out;
   a.win0 = win0; a.nwin = nwin; a.f0 = f0; a.f1 = f1; a.d = d; a.dst = dst;
+  a.o0 = o0; a.o1 = o1; a.slice_dim = slice_dim;
   a.sd = dst_stride_d; a.sw = dst_stride_win; a.sr = dst_stride_row; a.sc = dst_stride_col;
   a.fast_is_win = (dst_stride_win == 1 && dst_stride_col != 1) ? 1 : 0;
   int64_t blocks;
-  if (a.fast_is_win) { a.tiles_fast = (nwin + PT - 1) / PT; blocks = (int64_t)f0 * f1 * a.tiles_fast * (d / PT); }
-  else               { a.tiles_fast = (f1 + PT - 1) / PT;   blocks = (int64_t)f0 * nwin * a.tiles_fast * (d / PT); }
+  if (a.fast_is_win) { a.tiles_fast = (nwin + PT - 1) / PT; blocks = (int64_t)o0 * o1 * a.tiles_fast * (d / PT); }
+  else               { a.tiles_fast = (o1 + PT - 1) / PT;   blocks = (int64_t)o0 * nwin * a.tiles_fast * (d / PT); }
   if (blocks > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(pool_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  if (global_mean && n_out == 1 && o0 == 1 && o1 == 1) {     // (then the one window is every slice: lo = 0, hi = total)
+    const int64_t tok = (int64_t)f0 * f1;
+    hipLaunchKernelGGL(mean_all_kernel, dim3((unsigned)(d / 8)), dim3(256), 0, (hipStream_t)stream, k_slices,
+                       (lo - k_slice0) * tok, (hi - lo) * tok, d, dst, dst_stride_d);
+  } else if (o0 == f0 && o1 == f1)
+    hipLaunchKernelGGL(pool_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(pool_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   return vittf_check_launch();
+}
+
+// slice-axis pooling only: the in-plane output is the token grid (one-token windows: any slice_dim gives the same bits)
+extern "C" int vittf_pool_slices(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nslices, int32_t total_slices,
+                                 int32_t n_out, int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d,
+                                 uint16_t* dst, int64_t dst_stride_d, int64_t dst_stride_win, int64_t dst_stride_row,
+                                 int64_t dst_stride_col, void* stream) {
+  return pool_slices(k_slices, k_slice0, k_nslices, total_slices, n_out, win0, nwin, f0, f1, d, dst, dst_stride_d,
+                     dst_stride_win, dst_stride_row, dst_stride_col, f0, f1, 2, false, stream);
+}
+
+extern "C" int vittf_pool_slices3d(const uint16_t* k_slices, int32_t k_slice0, int32_t k_nslices, int32_t total_slices,
+                                   int32_t n_out, int32_t win0, int32_t nwin, int32_t f0, int32_t f1, int32_t d,
+                                   uint16_t* dst, int64_t dst_stride_d, int64_t dst_stride_win, int64_t dst_stride_row,
+                                   int64_t dst_stride_col, int32_t o0, int32_t o1, int32_t slice_dim, void* stream) {
+  return pool_slices(k_slices, k_slice0, k_nslices, total_slices, n_out, win0, nwin, f0, f1, d, dst, dst_stride_d,
+                     dst_stride_win, dst_stride_row, dst_stride_col, o0, o1, slice_dim, true, stream);
 }
 
 extern "C" int vittf_assemble_sum(const uint16_t* gz, const uint16_t* gy, const uint16_t* gx, int32_t nranks,

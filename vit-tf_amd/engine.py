@@ -124,5 +124,22 @@ class HipViT:
                                            _lib.stream_ptr())
         _lib.check(rc, 'vittf_vit_k_features')
 
+    def qkv_features(self, view, slice0, batch, outs):
+        """One forward of slices [slice0, slice0+batch) for several thirds of the hooked qkv tensor: `outs` maps a part
+        (0 q, 1 k, 2 v) to its output tensor, each written as k_features(part) writes it (same bits)."""
+        p = self.patch_size
+        tokens = (view.out_rows // p) * (view.out_cols // p) + 1
+        pos, _, _ = self.pos_for(view.out_rows, view.out_cols)
+        ws = self.workspace(batch, tokens)
+        ptrs = [None, None, None]
+        for part, out in outs.items():
+            assert out.dtype == torch.float16 and out.is_contiguous() and \
+                out.numel() >= batch * (tokens - 1) * self.embed_dim
+            ptrs[int(part)] = _lib.ptr(out)
+        mask = sum(1 << int(part) for part in outs)
+        rc = self.lib.vittf_vit_qkv_features(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
+                                             slice0, batch, mask, *ptrs, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, 'vittf_vit_qkv_features')
+
     def __call__(self, *_a, **_k):
         raise _lib.VittfError('HipViT is driven through compute_qkv / FeatureExtractor, not called on image tensors')

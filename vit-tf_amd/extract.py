@@ -138,6 +138,21 @@ def k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, part=1, out
     return out
 
 
+def qkv_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, parts=(0, 1, 2)):
+    """k_slices for several thirds of the hooked qkv tensor (`parts`: 0 q, 1 k, 2 v) from ONE engine forward per slice
+    batch: a list of tensors [s1-s0, f0*f1, D], in the order of `parts`, each with the bits k_slices(part) gives."""
+    _, _, _, _, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
+    engine_batch = engine_batch_for(f0 * f1 + 1, model.embed_dim, engine_batch)
+    n = s1 - s0
+    per = f0 * f1 * model.embed_dim
+    outs = [torch.empty((n, f0 * f1, model.embed_dim), dtype=torch.float16, device=model.device) for _ in parts]
+    view = dvol.view(axis, im_sizes)
+    flats = [o.view(-1) for o in outs]
+    for b0 in range(0, n, engine_batch):
+        model.qkv_features(view, s0 + b0, min(engine_batch, n - b0), {p: f[b0 * per:] for p, f in zip(parts, flats)})
+    return outs
+
+
 class HipOps:
     """The device operations the sharding logic below is written against: all of them libvittf kernels.
     (tests/ substitute a CPU stand-in built on the oracle to exercise the multi-rank logic under gloo;
@@ -149,6 +164,9 @@ class HipOps:
     def k_slices(self, model, dvol, axis, im_sizes, s0, s1, engine_batch, part):
         return k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch, part)
 
+    def qkv_slices(self, model, dvol, axis, im_sizes, s0, s1, engine_batch, parts):
+        return qkv_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch, parts)
+
     def zeros(self, shape, model):
         return torch.zeros(shape, dtype=torch.float16, device=model.device)
 
@@ -157,6 +175,13 @@ class HipOps:
         _lib.check(model.lib.vittf_pool_slices(_lib.ptr(kbuf), k_s0, kbuf.shape[0], n_slices_total, n_out, win0, nwin,
                                                f0, f1, d, _lib.ptr(dst), sd, sw, sr, sc, _lib.stream_ptr()),
                    'vittf_pool_slices')
+
+    def pool3d(self, model, kbuf, k_s0, n_slices_total, n_out, win0, nwin, f0, f1, d, dst, strides, o0, o1, slice_dim):
+        sd, sw, sr, sc = strides
+        _lib.check(model.lib.vittf_pool_slices3d(_lib.ptr(kbuf), k_s0, kbuf.shape[0], n_slices_total, n_out, win0, nwin,
+                                                 f0, f1, d, _lib.ptr(dst), sd, sw, sr, sc, o0, o1, slice_dim,
+                                                 _lib.stream_ptr()),
+                   'vittf_pool_slices3d')
 
     def assemble_sum(self, model, gz, gy, gx, world, chunks, d, feat_out):
         out = torch.empty((d, *feat_out), dtype=torch.float16, device=model.device)
@@ -181,28 +206,41 @@ def _slab_shape_strides(axis, d, n, chunk):
 
 
 def axis_features(model, dvol, axis, im_sizes, n_out, engine_batch=None, part=1, group=None,
-                  ops=_HIP_OPS, pending=None):
+                  ops=_HIP_OPS, pending=None, parts=None, in_plane=None):
     """Pooled (n_out windows along the slice dim) features of one axis, gathered over the process group.
 
     Returns (gathered [world, D, *slab_dims] fp16 device tensor, chunk).  With a `pending` list the exchange is only
     enqueued (RCCL runs it on its own stream while the next axis is computed) and the caller finishes it with
-    `finish_exchanges(pending)` before it reads `gathered`."""
+    `finish_exchanges(pending)` before it reads `gathered`.
+    `parts` (a list of thirds, instead of `part`): one engine forward per slice batch for all of them, and a slab of
+    len(parts) * D channels, part i at channel offset i * D -- still ONE exchange.  `in_plane` = (rows, cols) output
+    sizes of an in-plane adaptive pooling through vittf_pool_slices3d (default None: the token grid, vittf_pool_slices)."""
     world = torch.distributed.get_world_size(group) if _dist_on(group) else 1
     rank = torch.distributed.get_rank(group) if _dist_on(group) else 0
     sl, a, b, n_slices, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
     d = model.embed_dim
+    plist = [part] if parts is None else list(parts)
+    o0, o1 = (f0, f1) if in_plane is None else (int(in_plane[0]), int(in_plane[1]))
     n = [0, 0, 0]
-    n[sl], n[a], n[b] = n_out, f0, f1
+    n[sl], n[a], n[b] = n_out, o0, o1
     win0, nwin, chunk = shard_windows(n_out, rank, world)
-    shape, strides = _slab_shape_strides(axis, d, n, chunk)
+    shape, strides = _slab_shape_strides(axis, len(plist) * d, n, chunk)
     gathered = ops.zeros((world, *shape), model)
     slab = gathered[rank]
     if nwin > 0:
         s0 = window_bounds(win0, n_slices, n_out)[0]
         s1 = window_bounds(win0 + nwin - 1, n_slices, n_out)[1]
-        kbuf = ops.k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch, part)
-        ops.pool(model, kbuf, s0, n_slices, n_out, win0, nwin, f0, f1, d, slab, strides)
-        del kbuf
+        if len(plist) == 1:
+            kbufs = [ops.k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch, plist[0])]
+        else:
+            kbufs = ops.qkv_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch, plist)
+        for i, kbuf in enumerate(kbufs):
+            dst = slab if len(plist) == 1 else slab[i * d:(i + 1) * d]
+            if in_plane is None:
+                ops.pool(model, kbuf, s0, n_slices, n_out, win0, nwin, f0, f1, d, dst, strides)
+            else:
+                ops.pool3d(model, kbuf, s0, n_slices, n_out, win0, nwin, f0, f1, d, dst, strides, o0, o1, sl)
+        del kbufs, kbuf
     if _dist_on(group):
         handle = _all_gather_slabs(gathered, slab, group, defer=pending is not None)   # the one exchange step per axis
         if handle is not None:
@@ -289,14 +327,23 @@ def feature_volume(vol, model, feature_output_size=64, slice_along='all', engine
 
 
 def pooled_axis(vol, model, axis, im_sizes, out_size, engine_batch=None, part=1, group=None, dvol=None,
-                ops=_HIP_OPS):
-    """compute_qkv(..., pool_fn=AdaptiveAvgPool3d(out_size)) for one axis: (D, *out_size) fp16 on the device."""
+                ops=_HIP_OPS, parts=None):
+    """compute_qkv(..., pool_fn=AdaptiveAvgPool3d(out_size)) for one axis: (D, *out_size) fp16 on the device.
+    out_size is in volume dims (x, y, z) of the (D, x, y, z) un-pooled features; a None entry keeps that dim's size, as
+    torch's AdaptiveAvgPool3d does.  With `parts` (a list of thirds): {part: (D, *out_size)} from one engine forward per
+    slice batch and one exchange."""
     if dvol is None:
         dvol = ops.volume(vol, model)
-    sl, (a, b) = AXIS_DIMS[axis]
-    p = model.patch_size
-    if out_size[a] != im_sizes[a] // p or out_size[b] != im_sizes[b] // p:
-        raise NotImplementedError('in-plane pooling: the HIP path pools the slice axis only (the token grid already '
-                                  'equals feat_out_sz for every sizing infer.py produces, infer.py:317-319)')
-    g, _ = axis_features(model, dvol, axis, im_sizes, out_size[sl], engine_batch, part, group, ops)
-    return assemble_axis(g, axis, out_size[sl])
+    sl, a, b, n_slices, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
+    n_in = [0, 0, 0]
+    n_in[sl], n_in[a], n_in[b] = n_slices, f0, f1
+    size = [n_in[i] if s is None else int(s) for i, s in enumerate(out_size)]
+    # (an output of exactly (1, 1, 1) is torch's mean, not a pooling: vittf_pool_slices3d computes it, whatever the grid)
+    in_plane = None if (size[a], size[b]) == (f0, f1) and size != [1, 1, 1] else (size[a], size[b])
+    g, _ = axis_features(model, dvol, axis, im_sizes, size[sl], engine_batch, part, group, ops, parts=parts,
+                         in_plane=in_plane)
+    full = assemble_axis(g, axis, size[sl])
+    if parts is None:
+        return full
+    d = model.embed_dim
+    return {p: full[i * d:(i + 1) * d] for i, p in enumerate(parts)}
