@@ -49,13 +49,13 @@ int vittf_device_count(void);
 /* ------------------------------------------------------------------------------------------
  * ViT description.  Replaces the module tree of the upstream DINO VisionTransformer that the
  * reference fetches with torch.hub (infer.py:42-43, 323).  Head dim must be 64 (all DINO ViTs),
- * embed_dim a multiple of 128, patch 8 or 16.
+ * embed_dim a multiple of 128, patch 8, 14 or 16.
  * ---------------------------------------------------------------------------------------- */
 typedef struct vittf_vit_config {
   int32_t embed_dim;   /* D: 384 (ViT-S) / 768 (ViT-B) */
   int32_t depth;       /* L: 12 */
   int32_t heads;       /* D / 64 */
-  int32_t patch;       /* P: 8 */
+  int32_t patch;       /* P: 8, 14 (DINOv2) or 16 */
   int32_t dtype;       /* vittf_dtype of the MFMA operands */
   float   ln_eps;      /* 1e-6 */
   int32_t attention_fp8; /* 0: 16-bit attention (default).  1: the fp8 (e4m3) block-scaled MFMA attention path of BASELINE

@@ -7,7 +7,7 @@ kernels of libvittf instead of stock PyTorch ops.  There is no CPU path: ``--cpu
 compatibility and refused with exit code 1.
 
 Differences a caller can observe:
-  * the model comes from a LOCAL DINO state dict (``--weights``, ``$VITTF_WEIGHTS`` or the torch-hub
+  * the model comes from a LOCAL DINO / DINOv2 state dict (``--weights``, ``$VITTF_WEIGHTS`` or the torch-hub
     checkpoint cache) or from seeded synthetic weights (``--synthetic-weights SEED``); nothing is
     fetched from the network (the reference calls torch.hub.load, :42-43)
   * ``--batch-size`` no longer changes memory behaviour: slices are independent and the engine picks its
@@ -64,8 +64,8 @@ def norm_mean_std(t, mu=0, std=1):
 _MODEL_OPTS = {'weights': None, 'synthetic_seed': None, 'dtype': 'fp16', 'attention': '16bit'}
 
 
-def get_dino_model(name):
-    """HIP engine for ``dino_<name>``.  Weight source, in order: --weights / $VITTF_WEIGHTS, the local
+def _engine_model(name, hub):
+    """HIP engine for the hub entry ``<hub>_<name>``.  Weight source, in order: --weights / $VITTF_WEIGHTS, the local
     torch-hub checkpoint cache, --synthetic-weights / $VITTF_SYNTHETIC_WEIGHTS.  No network access."""
     path = _MODEL_OPTS['weights'] or vt.find_local_checkpoint(name)
     seed = _MODEL_OPTS['synthetic_seed']
@@ -74,18 +74,28 @@ def get_dino_model(name):
     if path is not None:
         sd = vt.load_state_dict_file(path)
     elif seed is not None:
-        print(f'Using seeded synthetic {name} weights (seed {seed}); features are NOT DINO features.')
+        print(f'Using seeded synthetic {name} weights (seed {seed}); features are NOT {hub.upper()} features.')
         sd = vt.synthetic_state_dict(name, seed)
     else:
-        print(f'No local checkpoint for dino_{name}: pass --weights PATH (DINO state dict) or '
+        print(f'No local checkpoint for {hub}_{name}: pass --weights PATH ({hub.upper()} state dict) or '
               f'--synthetic-weights SEED. This build never downloads weights.')
         sys.exit(1)
     return vt.HipViT(sd, name, dtype=_MODEL_OPTS['dtype'], attention=_MODEL_OPTS['attention'])
 
 
+def get_dino_model(name):
+    """HIP engine for ``dino_<name>`` (see _engine_model for where the weights come from)."""
+    return _engine_model(name, 'dino')
+
+
 def get_dinov2_model(name):
-    print('DINOv2 (patch 14) models are not supported by the HIP engine.')
-    sys.exit(1)
+    """HIP engine for ``dinov2_<name>`` (vits14 / vitb14 / vitl14): the same loading as get_dino_model; the LayerScale gammas
+    of the checkpoint are folded into the weights (vt.fold_layer_scale)."""
+    if name == 'vitg14':
+        print('dinov2_vitg14 is not supported by the HIP engine: its FFN is SwiGLU and its width D = 1536 is beyond the '
+              "engine's 1024.  Use vits14, vitb14 or vitl14.")
+        sys.exit(1)
+    return _engine_model(name, 'dinov2')
 
 
 def load_model(args):
@@ -257,7 +267,7 @@ def main(argv=None):
     parser.add_argument('--data-path', type=str, required=True, help='volume file (.npy / .pt) to extract features from')
     parser.add_argument('--cache-path', type=str, default=None, help='where the feature file goes (default: next to the volume)')
     parser.add_argument('--dino-model', type=str, choices=dino_archs, default=None, help='DINO ViT variant')
-    parser.add_argument('--dino2-model', type=str, choices=dino2_archs, default=None, help='DINOv2 variant (not available offline)')
+    parser.add_argument('--dino2-model', type=str, choices=dino2_archs, default=None, help='DINOv2 variant (patch 14; vitg14 is not supported: SwiGLU FFN, D = 1536)')
     parser.add_argument('--slice-along', type=str, choices=['x', 'y', 'z', 'all'], default='all',
                         help='Along which axis to slice volume, as it is fed slice-wise to DINO')
     parser.add_argument('--batch-size', type=int, default=1, help='a LOWER bound on the slices per engine call (the engine sizes its own calls: 256 x 4097 / tokens by '

@@ -54,7 +54,7 @@ WsLayout ws_layout(int d, int64_t rows, size_t fp8_bytes = 0) {
 
 bool config_ok(const vittf_vit_config* c) {
   return c && c->embed_dim > 0 && c->embed_dim % 128 == 0 && c->embed_dim <= 1024 && c->depth >= 1 &&
-         c->heads * 64 == c->embed_dim && (c->patch == 8 || c->patch == 16) &&
+         c->heads * 64 == c->embed_dim && (c->patch == 8 || c->patch == 14 || c->patch == 16) &&
          (c->dtype == VITTF_BF16 || c->dtype == VITTF_FP16) && c->ln_eps > 0.f;
 }
 }  // namespace

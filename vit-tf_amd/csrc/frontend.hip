@@ -5,8 +5,9 @@
 //   norm_minmax (infer.py:32-34), the 3-channel expand + ImageNet normalize (infer.py:154-155),
 //   F.interpolate(..., mode='nearest') (infer.py:177) and PatchEmbed + prepare_tokens of the upstream ViT.
 // The three input channels are the same grey value, so the conv is folded on the host to ONE input channel
-// (P*P taps) plus a bias; the arithmetic is fp32 VALU FMAs in the generic kernel and, for ViT-S/8, split-fp16 products on
-// the matrix cores that stay within 1e-6 of it (patch_embed_mfma_kernel): the precision of the first layer is kept.
+// (P*P taps) plus a bias; the arithmetic is fp32 VALU FMAs in the generic kernel and, for ViT-S/8 and DINOv2 ViT-S/14,
+// split-fp16 products on the matrix cores that stay within 1e-6 of it (patch_embed_mfma_kernel, patch_embed14_mfma_kernel):
+// the precision of the first layer is kept.
 #include "vittf_common.h"
 
 namespace {
@@ -242,6 +243,123 @@ __global__ __launch_bounds__(512, 1) void patch_embed_mfma_kernel(vittf_slice_vi
   }
 }
 
+// ---------------------------------------------------------------- patch embed on the matrix cores (D = 384, P = 14: DINOv2 ViT-S/14)
+// patch_embed_mfma_kernel's sum and precision contract (split-fp16 operands, hi.hi + lo.hi + hi.lo, within 1e-6 of the fp32
+// chain relative to a row's largest value, per-row arithmetic) for 14 x 14 patches:
+//   * k layout: one k step of 16 per patch row, its 14 pixels + 2 padded taps (zero weight, pixel forced to 0, never read):
+//     14 k steps, K = 224.  Lane (row, half h) holds pixels 8 h + e of patch row s -- the B operand's k = 16 s + 8 h + e;
+//   * all 12 output tiles would need 12 x 14 x {hi, lo} fragments of 1 KB = 336 KB of LDS (160 KB per CU): a workgroup owns ONE
+//     group of 4 output tiles (128 features, 112 KB), blockIdx.x % 3, for every row tile it visits -- the pixels of a row are
+//     gathered once per group (three times in all; they come from L2);
+//   * 4 accumulators (64 registers) + the 14 B operand pairs (112 registers); epilogue as in patch_embed_mfma_kernel.
+constexpr int PE14_P = 14, PE14_KS = 14, PE14_GROUPS = 3, PE14_TILES = PEM_D / 32 / PE14_GROUPS;   // 4 output tiles per group
+constexpr int PE14_FRAGS = PE14_TILES * PE14_KS * 2;                                                // 112 fragments of 1 KB
+__global__ __launch_bounds__(512, 1) void patch_embed14_mfma_kernel(vittf_slice_view view, int slice0, int batch,
+                                                                    const float* __restrict__ w_t,
+                                                                    const float* __restrict__ bias,
+                                                                    const float* __restrict__ cls_pos0,
+                                                                    const float* __restrict__ patch_pos,
+                                                                    float* __restrict__ tokens_out, int f0, int f1) {
+  __shared__ __attribute__((aligned(16))) unsigned short wlds[PE14_FRAGS * 512];      // 112 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int grp = blockIdx.x % PE14_GROUPS, wgs = gridDim.x / PE14_GROUPS;
+  const int col0 = 32 * PE14_TILES * grp;
+  // fragment (ot, s, hl), fr = ot * 14 + s: lane (i = l31, half hh) holds w[14 s + 8 hh + e][col0 + 32 ot + i] (0: padded tap)
+  for (int it = tid; it < (PE14_FRAGS / 2) * 64; it += 512) {
+    const int fr = it >> 6, ln = it & 63;
+    const int ot = fr / PE14_KS, s = fr - ot * PE14_KS;
+    const int i = ln & 31, hh = ln >> 5;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int kc = 8 * hh + e;
+      const float v = kc < PE14_P ? w_t[(int64_t)(PE14_P * s + kc) * PEM_D + col0 + 32 * ot + i] : 0.f;
+      const unsigned short hi = f32_to_f16bits(v);
+      const unsigned short lo = f32_to_f16bits(v - f16bits_to_f32(hi));
+      wlds[((fr * 2 + 0) * 64 + ln) * 8 + e] = hi;
+      wlds[((fr * 2 + 1) * 64 + ln) * 8 + e] = lo;
+    }
+  }
+  __syncthreads();
+  const int npatch = f0 * f1, tokens = npatch + 1;
+  const int64_t rows = (int64_t)batch * tokens;
+  const float lo_v = view.minmax[0], range = view.minmax[1] - view.minmax[0];
+  const float sr = (float)view.in_rows / (float)view.out_rows;
+  const float sc = (float)view.in_cols / (float)view.out_cols;
+  const int64_t ntile = (rows + 255) / 256;
+  for (int64_t tile = blockIdx.x / PE14_GROUPS; tile < ntile; tile += wgs) {
+    const int64_t r = tile * 256 + wave * 32 + l31;
+    const bool valid = r < rows;
+    const int b = valid ? (int)(r / tokens) : 0;
+    const int t = valid ? (int)(r - (int64_t)b * tokens) : 0;
+    const bool patch = valid && t > 0;
+    const int p = patch ? t - 1 : 0;
+    const int py = p / f1, pxx = p - py * f1;
+    const float* slice = view.vol + (int64_t)(slice0 + b) * view.stride_slice;
+    // source columns of the 8 image columns of this lane's half (nearest resize; half 1's last two are the padded taps)
+    int64_t coff[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int ix = pxx * PE14_P + 8 * h + e;
+      int cx = (int)floorf((float)ix * sc);
+      cx = cx < view.in_cols - 1 ? cx : view.in_cols - 1;
+      coff[e] = (int64_t)cx * view.stride_col;
+    }
+    f32x16_t acc[PE14_TILES];
+#pragma unroll
+    for (int j = 0; j < PE14_TILES; ++j)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[j][q] = 0.f;
+    // (two k steps per iteration: the pixel loads of all 14 would be hoisted in front of the MFMAs and spill)
+#pragma unroll 2
+    for (int s = 0; s < PE14_KS; ++s) {
+      // the B operands of k step s = patch row s, 8 columns
+      const int iy = py * PE14_P + s;
+      int ry = (int)floorf((float)iy * sr);
+      ry = ry < view.in_rows - 1 ? ry : view.in_rows - 1;
+      const float* srow = slice + (int64_t)ry * view.stride_row;
+      s16x8_t bh, bl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float v = 0.f;
+        if (patch && 8 * h + e < PE14_P) v = (srow[coff[e]] - lo_v) / range;
+        const unsigned short hi = f32_to_f16bits(v);
+        const unsigned short lo = f32_to_f16bits(v - f16bits_to_f32(hi));
+        bh[e] = (short)hi; bl[e] = (short)lo;
+      }
+#pragma unroll
+      for (int j = 0; j < PE14_TILES; ++j) {
+        const int fr = j * PE14_KS + s;
+        const s16x8_t ah = *reinterpret_cast<const s16x8_t*>(&wlds[((fr * 2 + 0) * 64 + lane) * 8]);
+        const s16x8_t al = *reinterpret_cast<const s16x8_t*>(&wlds[((fr * 2 + 1) * 64 + lane) * 8]);
+        acc[j] = mfma32<VITTF_FP16>(ah, bh, acc[j]);
+        acc[j] = mfma32<VITTF_FP16>(al, bh, acc[j]);
+        acc[j] = mfma32<VITTF_FP16>(ah, bl, acc[j]);
+      }
+    }
+    if (valid) {
+      float* orow = tokens_out + r * PEM_D;
+      const float* prow = patch_pos + (int64_t)p * PEM_D;
+#pragma unroll
+      for (int j = 0; j < PE14_TILES; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int c = col0 + 32 * j + 8 * g + 4 * h;
+          float4 o;
+          if (patch) {
+            const float4 bv = *reinterpret_cast<const float4*>(bias + c);
+            const float4 pv = *reinterpret_cast<const float4*>(prow + c);
+            o.x = acc[j][4 * g + 0] + bv.x + pv.x; o.y = acc[j][4 * g + 1] + bv.y + pv.y;
+            o.z = acc[j][4 * g + 2] + bv.z + pv.z; o.w = acc[j][4 * g + 3] + bv.w + pv.w;
+          } else {
+            o = *reinterpret_cast<const float4*>(cls_pos0 + c);
+          }
+          *reinterpret_cast<float4*>(orow + c) = o;
+        }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" size_t vittf_minmax_workspace_bytes(void) { return 2 * MM_BLOCKS * sizeof(float); }
@@ -266,26 +384,47 @@ extern "C" int vittf_patch_embed(const vittf_vit_config* cfg, const vittf_vit_we
   if (!w->pe_w_t || !w->pe_b || !pos->cls_plus_pos0 || !pos->patch_pos || !view->vol || !view->minmax)
     return VITTF_ERR_INVALID_ARG;
   const int p = cfg->patch;
-  if ((p != 8 && p != 16) || view->out_rows % p || view->out_cols % p || view->out_rows <= 0 || view->out_cols <= 0)
+  if ((p != 8 && p != 14 && p != 16) || view->out_rows % p || view->out_cols % p || view->out_rows <= 0 || view->out_cols <= 0)
     return VITTF_ERR_INVALID_ARG;
   if (view->in_rows <= 0 || view->in_cols <= 0 || batch > 65535) return VITTF_ERR_INVALID_ARG;
   const int f0 = view->out_rows / p, f1 = view->out_cols / p;
   const int nblk = (f0 * f1 + TP - 1) / TP;
   hipStream_t st = (hipStream_t)stream;
-  if (cfg->embed_dim == PEM_D && p == 8 && (((uintptr_t)w->pe_b | (uintptr_t)pos->cls_plus_pos0 | (uintptr_t)pos->patch_pos | (uintptr_t)tokens_out) & 15) == 0) {
+  const bool aligned = (((uintptr_t)w->pe_b | (uintptr_t)pos->cls_plus_pos0 | (uintptr_t)pos->patch_pos | (uintptr_t)tokens_out) & 15) == 0;
+  if (cfg->embed_dim == PEM_D && p == 8 && aligned) {
     // ViT-S/8: the conv on the matrix cores with fp16 head + tail operands (see patch_embed_mfma_kernel)
     const int cus = vittf_current_cus();
     if (cus <= 0) return VITTF_ERR_NO_DEVICE;
     const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1) + 255) / 256;
+    vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_mfma_kernel");
     hipLaunchKernelGGL(patch_embed_mfma_kernel, dim3((unsigned)(ntile < cus ? ntile : cus)), dim3(512), 0, st, *view, slice0, batch,
+                       w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1);
+    return vittf_check_launch();
+  }
+  if (cfg->embed_dim == PEM_D && p == PE14_P && aligned) {
+    // DINOv2 ViT-S/14: the same on the matrix cores, one workgroup per group of 4 output tiles (patch_embed14_mfma_kernel)
+    const int cus = vittf_current_cus();
+    if (cus <= 0) return VITTF_ERR_NO_DEVICE;
+    const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1) + 255) / 256;
+    const int per_group = cus / PE14_GROUPS > 0 ? cus / PE14_GROUPS : 1;
+    const int wgs = (int)(ntile < per_group ? ntile : per_group);
+    vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed14_mfma_kernel");
+    hipLaunchKernelGGL(patch_embed14_mfma_kernel, dim3((unsigned)(PE14_GROUPS * wgs)), dim3(512), 0, st, *view, slice0, batch,
                        w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1);
     return vittf_check_launch();
   }
   const int threads = cfg->embed_dim % 384 == 0 ? 384 : 256;   // one feature per thread in a single pass for D = 384 / 768
   if (p == 8) {
+    vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<8>");
     hipLaunchKernelGGL((patch_embed_kernel<8>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
                        pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
+  } else if (p == 14) {
+    // 196 taps = 49 steps of the kernel's 4-k loop
+    vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<14>");
+    hipLaunchKernelGGL((patch_embed_kernel<14>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
+                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
   } else {
+    vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<16>");
     hipLaunchKernelGGL((patch_embed_kernel<16>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
                        pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
   }

@@ -10,7 +10,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .weights import arch_of, fold_patch_embed, interpolate_pos_embed, pack_block_tail_weights, pack_row_images
+from .weights import (arch_of, fold_layer_scale, fold_patch_embed, interpolate_pos_embed, pack_block_tail_weights,
+                      pack_row_images)
 
 _TORCH_DT = {_lib.BF16: torch.bfloat16, _lib.FP16: torch.float16}
 
@@ -28,7 +29,8 @@ class _Block:
 class HipViT:
     """Weights + workspace of one ViT on one GPU.
 
-    state_dict: DINO-layout tensors (fp32, CPU or GPU).  arch: DINO name ('vits8', ...) or
+    state_dict: DINO-layout tensors (fp32, CPU or GPU; DINOv2's LayerScale gammas are folded in).  arch: DINO / DINOv2 name
+    ('vits8', 'vits14', ...) or
     (embed_dim, depth, heads, patch).  dtype of the MFMA operands: 'fp16' (default: the reference's own GPU autocast
     type, infer.py:309; meets the 1e-3 parity bound against the fp32 CPU path) or 'bf16' (opt-in: 8-bit mantissa,
     2.4e-3 .. 3.9e-3 against the CPU path).  attention: '16bit' (default) or 'fp8' -- BASELINE configs[3]'s fp8 MFMA
@@ -53,6 +55,9 @@ class HipViT:
         self.cfg = _lib.VitConfig(dim, depth, heads, patch, self.dtype_id, 1e-6, 1 if attention == 'fp8' else 0, int(flags))
 
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items()}
+        # DINOv2 LayerScale (blocks.{i}.ls1 / ls2.gamma present, whatever the arch name): folded into attn.proj / mlp.fc2 in
+        # fp32 before the one conversion to 16 bits -- the kernels see ordinary weights
+        sd = fold_layer_scale(sd)
         h16 = _TORCH_DT[self.dtype_id]
         dev = self.device
 

@@ -24,7 +24,7 @@ AXIS_DIMS = {'z': (2, (0, 1)), 'y': (1, (0, 2)), 'x': (0, (1, 2))}
 # projection's tiles and 32.01 of the block tail's -- a seventeenth / thirty-third round for one tile in 256 --, 512 slices
 # halve that waste: 2318 -> 2340 slices/s on one box (block tail 3.07 -> 2.96 ms per 256 slices, qkv 0.989 -> 0.976; round 5).
 # 512 slices of N = 4097 tokens at D = 384 = 11 GB of workspace (of 288 GB).  D = 768 stays at 256: its widest buffer (rows x
-# 4 D 16-bit values) must stay below 2^32 elements.
+# 4 D 16-bit values) must stay below 2^32 elements; D = 1024 (ViT-L/14) is capped below that (wide_batch_limit: 255 slices).
 DEFAULT_ENGINE_BATCH = 512
 DEFAULT_ENGINE_BATCH_WIDE = 256       # embed_dim > 384
 MAX_ENGINE_BATCH_ROWS = 1024 * 4097   # what an AtLeast request may raise a call to (32-bit offsets into the widest buffers)
@@ -49,12 +49,26 @@ def engine_batch_for(tokens, embed_dim, requested=None):
         return max(1, int(env))
     base = DEFAULT_ENGINE_BATCH if int(embed_dim) <= 384 else DEFAULT_ENGINE_BATCH_WIDE
     default = max(1, min(base, base * 4097 // int(tokens)))
+    if int(embed_dim) > 768:
+        # ViT-L (D = 1024): 256 slices of N = 4097 are 4.296e9 hidden values, over 2^32 -- cap the default and AtLeast
+        default = min(default, wide_batch_limit(tokens, embed_dim))
     if isinstance(requested, AtLeast):
         # (capped: the widest buffers of a call -- rows x 4 D 16-bit values, the fp8 operand rows -- are addressed with 32-bit offsets)
-        return min(max(int(requested), default), max(default, MAX_ENGINE_BATCH_ROWS // int(tokens)))
+        got = min(max(int(requested), default), max(default, MAX_ENGINE_BATCH_ROWS // int(tokens)))
+        return min(got, wide_batch_limit(tokens, embed_dim)) if int(embed_dim) > 768 else got
     if requested:
         return max(1, int(requested))
     return default
+
+
+def wide_batch_limit(tokens, embed_dim):
+    """Most slices of `tokens` tokens one engine call of width `embed_dim` takes: its [rows][4 D] hidden buffer below 2^32
+    elements (vittf_vit_qkv_features refuses more) and each K-feature output, batch x (tokens - 1) x D fp16 values, below
+    2^31 bytes (the persistent GEMM's dropped-row offset 0x80000000 must lie outside it).  N = 4097, D = 1024: 255 slices."""
+    tokens, d = int(tokens), int(embed_dim)
+    by_hidden = (2 ** 32 - 1) // (tokens * 4 * d)
+    by_kfeat = (2 ** 31 - 1) // (max(1, tokens - 1) * d * 2)
+    return max(1, min(by_hidden, by_kfeat))
 
 
 PARTS = {'q': 0, 'k': 1, 'v': 2}

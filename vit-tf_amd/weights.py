@@ -1,11 +1,18 @@
-"""Weights of the DINO ViT in the upstream state-dict layout: local loading, a seeded synthetic
-recipe, and the host-side preprocessing the HIP engine needs (channel folding, position embedding).
+"""Weights of the DINO / DINOv2 ViT in the upstream state-dict layout: local loading, a seeded synthetic
+recipe, and the host-side preprocessing the HIP engine needs (channel folding, LayerScale folding, position embedding).
 
 The reference fetches the model over the network (``torch.hub.load('facebookresearch/dino:main',
 'dino_vits8')``, infer.py:42-43).  Here weights come from a LOCAL state-dict file (same key names as the
 DINO checkpoints: ``cls_token``, ``pos_embed``, ``patch_embed.proj.*``, ``blocks.{i}.norm1|attn.qkv|
 attn.proj|norm2|mlp.fc1|mlp.fc2.*``, ``norm.*``) or from the seeded synthetic recipe below when no
 checkpoint is available (benchmarks, tests).
+
+DINOv2 (facebookresearch/dinov2, hub entries ``dinov2_vit{s,b,l,g}14``; upstream code is not vendored, these facts are
+restated from it like SURVEY.md 8a row a5 restates DINO's): ``img_size=518, patch_size=14, init_values=1.0``,
+``ffn_layer="mlp"`` (g14: ``"swiglufused"``), no register tokens, ``interpolate_offset=0.1`` with the same bicubic
+scale-factor resize as DINO (stored grid 37 x 37).  Its block is ``x + ls1(attn(norm1(x)))``, ``x + ls2(mlp(norm2(x)))``
+with ``ls(y) = y * gamma`` (one gamma per channel): the checkpoint holds the DINO keys plus ``blocks.{i}.ls1.gamma``,
+``blocks.{i}.ls2.gamma`` and ``mask_token`` (unused at inference).
 """
 import math
 import os
@@ -19,13 +26,22 @@ ARCHS = {
     'vits16': (384, 12, 6, 16),
     'vitb8': (768, 12, 12, 8),
     'vitb16': (768, 12, 12, 16),
+    # hub entries dinov2_<name> (LayerScale blocks; see the module docstring).  vitg14 (SwiGLU FFN, D = 1536) is not built.
+    'vits14': (384, 12, 6, 14),
+    'vitb14': (768, 12, 12, 14),
+    'vitl14': (1024, 24, 16, 14),
 }
+DINOV2_ARCHS = ('vits14', 'vitb14', 'vitl14')
+DINOV2_STORED_GRID = 37                 # 518 / 14
 # file names torch.hub would have cached for these entries
 HUB_FILES = {
     'vits8': 'dino_deitsmall8_pretrain.pth',
     'vits16': 'dino_deitsmall16_pretrain.pth',
     'vitb8': 'dino_vitbase8_pretrain.pth',
     'vitb16': 'dino_vitbase16_pretrain.pth',
+    'vits14': 'dinov2_vits14_pretrain.pth',
+    'vitb14': 'dinov2_vitb14_pretrain.pth',
+    'vitl14': 'dinov2_vitl14_pretrain.pth',
 }
 IN_MEAN = (0.485, 0.456, 0.406)   # infer.py:39
 IN_STD = (0.229, 0.224, 0.225)    # infer.py:40
@@ -45,8 +61,13 @@ def arch_of(arch):
 OUTLIER_CHANNELS = (7, 100, 191, 250, 333, 380)
 
 
-def synthetic_state_dict(arch='vits8', seed=0, stored_grid=28, outliers=False):
+def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False, layer_scale=None):
     """Seeded random weights with the DINO key layout.
+
+    stored_grid: side of the stored position-embedding grid (default 28, 37 for the DINOv2 names).
+    layer_scale: add the DINOv2 keys -- ``blocks.{i}.ls1.gamma`` / ``ls2.gamma``, log-uniform over [1e-5, 1] so that tiny
+    gammas are exercised, and ``mask_token`` (default: True for the DINOv2 names only).  They are drawn from a generator of
+    their own, after every DINO tensor, so the DINO tensors of a seed do not depend on this flag.
 
     outliers=True: the same weights with six massive channels planted -- x50 rows in two blocks' mlp.fc2 and one block's
     attn.proj (the residual stream then carries them to the end), x50 entries in several norm weights (16-bit LayerNorm
@@ -60,6 +81,11 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=28, outliers=False):
     ordering / bias / masking mistakes and gives realistic data for benchmarking.
     """
     dim, depth, heads, patch = arch_of(arch)
+    dinov2 = isinstance(arch, str) and arch in DINOV2_ARCHS
+    if stored_grid is None:
+        stored_grid = DINOV2_STORED_GRID if dinov2 else 28
+    if layer_scale is None:
+        layer_scale = dinov2
     g = torch.Generator().manual_seed(seed)
 
     def rnd(*shape, std=1.0):
@@ -106,7 +132,33 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=28, outliers=False):
         for head, ch, a in ((1 % heads, c[0], 0.5), (2 % heads, c[5], 0.5)):
             wq[head * 64:(head + 1) * 64, ch] += a
             wq[dim + head * 64:dim + (head + 1) * 64, ch] += a
+    if layer_scale:
+        g2 = torch.Generator().manual_seed(0x15ca1e + seed)
+        sd['mask_token'] = torch.randn(1, dim, generator=g2) * 0.5
+        for i in range(depth):
+            for ls in ('ls1', 'ls2'):
+                sd[f'blocks.{i}.{ls}.gamma'] = 10.0 ** (torch.rand(dim, generator=g2) * -5.0)
     return sd
+
+
+def fold_layer_scale(sd):
+    """DINOv2 LayerScale folded into the linear in front of it: ``ls1(proj(y)) = (diag(g) W) y + g * b`` for attn.proj,
+    the same with ls2 for mlp.fc2.  fp32, on the host, before the engine's one conversion of the weights to 16 bits (exact
+    in real arithmetic; DESIGN.md section 5 bounds what the fp16 weights lose).  Returns a new dict without the ``ls*``
+    keys; a dict without them is returned unchanged (the same tensors)."""
+    if not any(k.endswith(('.ls1.gamma', '.ls2.gamma')) for k in sd):
+        return sd
+    out = {k: v for k, v in sd.items() if not k.endswith(('.ls1.gamma', '.ls2.gamma'))}
+    i = 0
+    while f'blocks.{i}.attn.proj.weight' in sd:
+        for ls, lin in (('ls1', 'attn.proj'), ('ls2', 'mlp.fc2')):
+            key = f'blocks.{i}.{ls}.gamma'
+            if key in sd:
+                gamma = sd[key].float()
+                out[f'blocks.{i}.{lin}.weight'] = sd[f'blocks.{i}.{lin}.weight'].float() * gamma[:, None]
+                out[f'blocks.{i}.{lin}.bias'] = sd[f'blocks.{i}.{lin}.bias'].float() * gamma
+        i += 1
+    return out
 
 
 def load_state_dict_file(path):
@@ -153,7 +205,8 @@ def fold_patch_embed(weight, bias):
         sum_c W[d,c,i,j] * (x - mean_c) / std_c + b[d]
       = sum_ij (sum_c W[d,c,i,j] / std_c) * x_ij + (b[d] - sum_c mean_c / std_c * sum_ij W[d,c,i,j])
 
-    (infer.py:39-40, 154-155 + upstream PatchEmbed).  Returns (w_t [P*P][D], b [D]) fp32, folded in fp64.
+    (infer.py:39-40, 154-155 + upstream PatchEmbed).  Returns (w_t [P*P][D], b [D]) fp32, folded in fp64.  DINOv2's
+    PatchEmbed is the same conv with P = 14.
     """
     w = weight.double()
     mean = torch.tensor(IN_MEAN, dtype=torch.float64).view(1, 3, 1, 1)
