@@ -51,13 +51,13 @@ struct KfeatParts {
   int d;
 };
 
-template <int DT, int EPI, int NSTAGE>
-__global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const unsigned short* __restrict__ A,
+template <int DT, int EPI>
+__global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __restrict__ A,
                                                       const unsigned short* __restrict__ W,
                                                       const float* __restrict__ bias, void* __restrict__ out,
                                                       int64_t rows, int n, int k, int tokens, int n_tiles,
                                                       int total_tiles, KfeatParts kp) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][A tile | W tile]
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [A tile | W tile], then the epilogue's C tile
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -109,32 +109,14 @@ __global__ __launch_bounds__(256, NSTAGE == 1 ? 4 : 2) void gemm_kernel(const un
         for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = mfma32<DT>(wf[ni], af[mi], acc[ni][mi]);
     }
   };
-  if constexpr (NSTAGE == 1) {
-    // one 32 KB stage, four workgroups per CU: the other workgroups' MFMAs cover this one's load latency
-    for (int t = 0; t < nk; ++t) {
-      stage_tile(A, k, m0, rows - 1, t * BK, lds_wave, tid, voff);
-      stage_tile(W, k, n0, n - 1, t * BK, lds_wave + TILE_BYTES, tid, voff);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      compute_tile(smem, smem + TILE_BYTES);
-      __syncthreads();
-    }
-  } else {
-    stage_tile(A, k, m0, rows - 1, 0, lds_wave, tid, voff);
-    stage_tile(W, k, n0, n - 1, 0, lds_wave + TILE_BYTES, tid, voff);
+  // one 32 KB stage, four workgroups per CU: the other workgroups' MFMAs cover this one's load latency
+  for (int t = 0; t < nk; ++t) {
+    stage_tile(A, k, m0, rows - 1, t * BK, lds_wave, tid, voff);
+    stage_tile(W, k, n0, n - 1, t * BK, lds_wave + TILE_BYTES, tid, voff);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int t = 0; t < nk; ++t) {
-      char* cur = smem + (t & 1) * 2 * TILE_BYTES;
-      if (t + 1 < nk) {
-        const unsigned nxt = lds_wave + ((t + 1) & 1) * 2 * TILE_BYTES;
-        stage_tile(A, k, m0, rows - 1, (t + 1) * BK, nxt, tid, voff);
-        stage_tile(W, k, n0, n - 1, (t + 1) * BK, nxt + TILE_BYTES, tid, voff);
-      }
-      compute_tile(cur, cur + TILE_BYTES);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+    compute_tile(smem, smem + TILE_BYTES);
+    __syncthreads();
   }
 
   // ---- epilogue ----
@@ -246,28 +228,15 @@ int launch_gemm(const void* a, const void* w, const float* bias, void* out, int6
   // (EPI_KFEAT_PARTS: n = 3 d weight rows, part_tiles = the requested thirds' column tiles)
   const int m_tiles = (int)((rows + BM - 1) / BM), n_tiles = epi == EPI_KFEAT_PARTS ? part_tiles : n / BN;
   const int total = m_tiles * n_tiles;
-  // 1 = one 32 KB operand stage and four workgroups per CU (default: +16 % on the K = 384 shapes, whose six
-  // K steps are too short for a two-stage pipeline to cover the load latency); 2 = double buffer, two per CU
-  constexpr int nstage = 1;      // (one 32 KB stage x four workgroups per CU; the double-buffered form measured slower on every shape)
-  const size_t lds = nstage == 1 ? (size_t)BM * (BN * 2 + 16) : (size_t)4 * TILE_BYTES;   // stage(s) / padded C tile (16-bit: 128 x 272 B; fp32 half tile: 128 x 272 B)
+  // one stage, not two: +16 % on the K = 384 shapes, whose six K steps are too short for a double buffer to pay
+  const size_t lds = (size_t)BM * (BN * 2 + 16);   // 32 KB stage / padded C tile (16-bit: 128 x 272 B; fp32 half tile: 128 x 272 B)
   const unsigned short* A = (const unsigned short*)a;
   const unsigned short* Wp = (const unsigned short*)w;
 #define VITTF_GEMM_CASE(E)                                                                                   \
-  case E: {                                                                                                  \
-    static bool attr_set = false;                                                                            \
-    if (!attr_set) {                                                                                         \
-      (void)hipFuncSetAttribute((const void*)gemm_kernel<DT, E, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)(4 * TILE_BYTES));                                                      \
-      attr_set = true;                                                                                       \
-    }                                                                                                        \
-    if (nstage == 1)                                                                                         \
-      hipLaunchKernelGGL((gemm_kernel<DT, E, 1>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k, \
-                         tokens, n_tiles, total, kp);                                                        \
-    else                                                                                                     \
-      hipLaunchKernelGGL((gemm_kernel<DT, E, 2>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k, \
-                         tokens, n_tiles, total, kp);                                                        \
-    break;                                                                                                   \
-  }
+  case E:                                                                                                    \
+    hipLaunchKernelGGL((gemm_kernel<DT, E>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k,  \
+                       tokens, n_tiles, total, kp);                                                          \
+    break;
   switch (epi) {
     VITTF_GEMM_CASE(VITTF_EPI_BIAS)
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_GELU)

@@ -23,13 +23,6 @@
 
 namespace {
 
-#ifndef AS_VARIANT      // timing-only builds (tools/gemm_as_ab.py; never in libvittf.so): 1 no stores, 2 no staging, 4 no LDS-DMA in the loop
-#define AS_VARIANT 0
-#endif
-#ifndef AS_STORE_AUX      // cache policy of the output stores: 2 = non-temporal (every byte is written once; the weights live in L2)
-#define AS_STORE_AUX 0
-#endif
-constexpr bool V_NO_STORE = AS_VARIANT & 1, V_NO_STAGE = AS_VARIANT & 2, V_NO_DMA = AS_VARIANT & 4;
 constexpr int K = 384;
 constexpr int SB = 24576;                    // bytes of one weight image = one ring step: [32 output columns][384 k]
 constexpr int NSLOT = 4, AHEAD = NSLOT - 1;
@@ -133,9 +126,10 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
       pk[1] = pack2_h16<DT>((q[4 * gq + 2] + b[2]) * qsc, (q[4 * gq + 3] + b[3]) * qsc);
       *(lds_w2_ptr)(stg_w + (storer ? 0 : ((u >> 1) & 1) * STG) + 64 * (u & 1) + 16 * gq) = pk;
     };
-    // (storer waves) units 2 m, 2 m + 1 = 64 columns = 128 bytes of a row: the wave's own rows, or its partner's (32 rows up)
+    // (storer waves) units 2 m, 2 m + 1 = 64 columns = 128 bytes of a row: the wave's own rows, or its partner's (32 rows up);
+    // plain stores (sc0 or non-temporal ones: no gain, up to 2 % slower)
     auto store_pair = [&](int m, bool partner) {
-      if (V_NO_STORE || !storer) return;
+      if (!storer) return;
       const unsigned rd = partner ? stg_rp + (m & 1) * STG : stg_r;
       f32x4_t rbk[4];
 #pragma unroll
@@ -143,7 +137,7 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, rbk[i]), ro, oo + (partner ? -128 * row_bytes_out : 0) + m * 128,
-                                               i * 8 * row_bytes_out, AS_STORE_AUX);
+                                               i * 8 * row_bytes_out, 0);
     };
     // one unit: 24 MFMAs acc = W(u) . A^T from zero; the unit before it staged in the gaps.  WAITN: vector-memory operations
     // of this wave that may be in flight at its start (the pieces of the step before, stores, the row loads of a new tile).
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
       constexpr int WAITN = decltype(WAITc)::value;
       load_bias(u, bcur);
       if (storer) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(V_NO_DMA ? 0 : WAITN) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(WAITN) : "memory");
       if (u >= 3 && (u & 1)) store_pair((u - 3) >> 1, true);      // the partner's pair, staged during the last two units
       const int g_next = g + AHEAD < units ? g + AHEAD : g + AHEAD - units;
       const int slot_free = slot == 0 ? NSLOT - 1 : slot - 1;
@@ -164,8 +158,8 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
           for (int i = 0; i < 4; ++i) { base[i] += d_; asm volatile("" : "+v"(base[i])); }
         }
         wf[j % NF] = *(lds_frag_ptr)(base[((j + NF) % 24) & 3] + (((j + NF) % 24) >> 2) * 4096);
-        if (!V_NO_DMA && !storer && j % 4 == 3) lds_dma16_keep(rsrc, lds0 + slot_free * SB + src0 + (j >> 2) * 1024, lane * 16, g_next * SB + src0 + (j >> 2) * 1024);
-        if (!V_NO_STAGE && stage_prev && j % 6 == 2) stage(prevq, bprev, u - 1, j / 6);
+        if (!storer && j % 4 == 3) lds_dma16_keep(rsrc, lds0 + slot_free * SB + src0 + (j >> 2) * 1024, lane * 16, g_next * SB + src0 + (j >> 2) * 1024);
+        if (stage_prev && j % 6 == 2) stage(prevq, bprev, u - 1, j / 6);
         __builtin_amdgcn_sched_barrier(0);
       }
       g = g + 1 == units ? 0 : g + 1;
@@ -196,10 +190,6 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
 }
 
 }  // namespace
-
-#ifdef AS_STANDALONE
-void vittf_note_kernel(int, const char*) {}
-#endif
 
 extern "C" size_t vittf_gemm_as_workspace_bytes(void) { return sizeof(unsigned); }
 

@@ -4,8 +4,8 @@
 // Round 4 (BASELINE configs[3]).  gemm.hip's 128 x 128 x 64 tiles (one stage, four workgroups per CU) run these shapes at
 // 740-870 TFLOP/s.  Earlier forms of this file are in the history with their numbers (LAB_NOTES.md, former DESIGN section 4, "Round 4: the
 // ViT-B linears": a pipelined 256 x 128 kernel with two workgroups per CU; an 8-wave ping-pong kernel with a load segment
-// and an MFMA segment per K step -- hence the file's name; the same made persistent); timing-only builds of each
-// (tools/pp_variants.sh) said where its time went.  This form:
+// and an MFMA segment per K step -- hence the file's name; the same made persistent); timing-only builds of each said where
+// its time went (profiles/r04*_gemm_pp*_variants.txt).  This form:
 //   * workgroup = 8 waves on a 256 x 256 output tile, persistent (one per CU); wave (g, c) owns rows 128 g .. + 127 and
 //     columns 64 c .. + 63 = 4 x 2 accumulator tiles (128 VGPRs), computed transposed like the other GEMMs (weights = MFMA A
 //     operand, activations = B operand: a lane owns one activation row and 4 consecutive columns per register quad).
@@ -44,20 +44,11 @@ static_assert(PLDS <= 160 * 1024, "LDS");
 
 #define PP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
-// ---- timing-only variants for tools/pp_variants.sh (never in libvittf.so: the Makefile does not define PP_VARIANT) ----
-#ifndef PP_VARIANT
-#define PP_VARIANT 0
-#endif
-constexpr bool PV_NO_DMA = PP_VARIANT & 1;       // no LDS-DMA inside the K loop (wrong results)
-constexpr bool PV_NO_READS = PP_VARIANT & 4;     // no fragment reads inside the K loop (wrong results)
-
-constexpr bool PV_NO_EPI = PP_VARIANT & 32;      // no epilogue (wrong results)
-// cache policy bits of the epilogue's 16-bit buffer stores: non-temporal (bit 1) by default -- the 128 KB a tile writes do not
-// push the operand panels the next tiles re-read out of L2: +3.5-4 % on qkv / fc1 (profiles/r04e_gemm_pp_store_policy.txt: 871 ->
-// 902, 787 -> 818 TFLOP/s); variants 512 / 1024 / 2048 = plain / sc0 nt / sc0 sc1.  The fp32 residual stores stay plain (no
-// difference measured, and the LayerNorm launch behind fc2 re-reads those rows).
-constexpr int PV_ST_AUX = (PP_VARIANT & 512) ? 0 : (PP_VARIANT & 1024) ? 3 : (PP_VARIANT & 2048) ? 17 : 2;
-constexpr bool PV_NO_PIN = PP_VARIANT & 128;     // no scheduling fences inside the MFMA segment (the compiler places the reads)
+// cache policy bits of the epilogue's 16-bit buffer stores: non-temporal (bit 1) -- the 128 KB a tile writes do not push the
+// operand panels the next tiles re-read out of L2: +3.5-4 % on qkv / fc1 (profiles/r04e_gemm_pp_store_policy.txt: 871 -> 902,
+// 787 -> 818 TFLOP/s).  The fp32 residual stores stay plain (no difference measured, and the LayerNorm launch behind fc2
+// re-reads those rows).
+constexpr int PP_STORE_AUX = 2;
 
 // byte offset of 16-byte k-chunk kc (0..3) of row r inside a [R][32] operand image (two rows per 128-byte tile_off row)
 __device__ __forceinline__ int p_img_off(int r, int kc) { return tile_off(r >> 1, ((r & 1) << 2) | kc); }
@@ -214,9 +205,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
       acc[ni][mi] = mfma32<DT>(cur.w[ni][st], cur.a[mi][st], acc[ni][mi]);
       // the fragment order of the reads follows the order the NEXT stage's MFMAs need them in: w(0,0) a(0..3,0) w(1,0) ...
       constexpr int order[12] = {0, 4, 5, 6, 7, 1, 2, 8, 9, 10, 11, 3};
-      if (j < 12 && more && !PV_NO_READS) read_frag(nxt, order[j], ab, wb);
-      if ((j & 3) == 3 && !PV_NO_DMA) iss = dma_piece(j >> 2);
-      if (!PV_NO_PIN) __builtin_amdgcn_sched_barrier(0);
+      if (j < 12 && more) read_frag(nxt, order[j], ab, wb);
+      if ((j & 3) == 3) iss = dma_piece(j >> 2);
+      __builtin_amdgcn_sched_barrier(0);
     }
     if (more) r_slot = (r_slot + 1) & 3;
     __builtin_amdgcn_sched_barrier(0);
@@ -268,191 +259,180 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
     PP_BARRIER();                                // (every wave is past the tile's last MFMA and fragment read)
 
     // ---- epilogue: the accumulators hold C^T -- a lane owns activation row (per mi) and columns 32 ni + 8 g + 4 h + {0..3} ----
-    if constexpr (PV_NO_EPI) {
-      float sink = 0.f;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sink += acc[i][j][r];
-      if (sink == 1.2345f) reinterpret_cast<float*>(out)[tid] = sink;
-    } else {
-      // The tile leaves in eight parts of 32 rows x 256 columns.  Writers (the four waves of the part's group) put their raw
-      // fp32 accumulators into the staging area a row per lane (16-byte chunk index XOR row: conflict-free both ways); after
-      // the barrier ALL eight waves pick the part up as 1 KB row segments -- a thread owns four columns of four rows -- add
-      // apply the epilogue's function (the bias is already in: the accumulators started from it) and send the result off: 512-byte runs of 16-bit values, or the fp32
-      // read-modify-write of the residual stream (x of a part is requested before the part is staged).  Always four buffer
-      // stores per thread and part (rows past the end fall outside the descriptor): the counted waits of the next tile's
-      // first stage know the number.
-      char* stg = smem + PRING;
-      constexpr bool RES = EPI == VITTF_EPI_BIAS_RESIDUAL;
-      // residual: a thread owns 4 columns (one staged chunk) of 4 rows; 16-bit outputs: 8 columns (two chunks -> one 16-byte
-      // store: the epilogue is bound by the NUMBER of store instructions) of 2 rows
-      const int ch = RES ? (tid & 63) : 2 * (tid & 31);
-      [[maybe_unused]] const float qs = (n0 + 4 * ch) < n / 3 ? 0.125f * 1.44269504088896340736f : 1.0f;   // (uniform per tile when 256 | n / 3)
-      [[maybe_unused]] float vmax_a = 0.f, vmax_b = 0.f;     // (fp8 qkv epilogue, v tiles) this thread's maxima: first / second slice of the tile
-      [[maybe_unused]] int64_t fb0 = 0;
-      if constexpr (EPI == PP_EPI_QKV_FP8) fb0 = m0 / tokens;
+    // The tile leaves in eight parts of 32 rows x 256 columns.  Writers (the four waves of the part's group) put their raw
+    // fp32 accumulators into the staging area a row per lane (16-byte chunk index XOR row: conflict-free both ways); after
+    // the barrier ALL eight waves pick the part up as 1 KB row segments -- a thread owns four columns of four rows -- add
+    // apply the epilogue's function (the bias is already in: the accumulators started from it) and send the result off: 512-byte runs of 16-bit values, or the fp32
+    // read-modify-write of the residual stream (x of a part is requested before the part is staged).  Always four buffer
+    // stores per thread and part (rows past the end fall outside the descriptor): the counted waits of the next tile's
+    // first stage know the number.
+    char* stg = smem + PRING;
+    constexpr bool RES = EPI == VITTF_EPI_BIAS_RESIDUAL;
+    // residual: a thread owns 4 columns (one staged chunk) of 4 rows; 16-bit outputs: 8 columns (two chunks -> one 16-byte
+    // store: the epilogue is bound by the NUMBER of store instructions) of 2 rows
+    const int ch = RES ? (tid & 63) : 2 * (tid & 31);
+    [[maybe_unused]] const float qs = (n0 + 4 * ch) < n / 3 ? 0.125f * 1.44269504088896340736f : 1.0f;   // (uniform per tile when 256 | n / 3)
+    [[maybe_unused]] float vmax_a = 0.f, vmax_b = 0.f;     // (fp8 qkv epilogue, v tiles) this thread's maxima: first / second slice of the tile
+    [[maybe_unused]] int64_t fb0 = 0;
+    if constexpr (EPI == PP_EPI_QKV_FP8) fb0 = m0 / tokens;
 #pragma unroll 1
-      for (int sp = 0; sp < 8; ++sp) {
-        const int pg = sp >> 2, pm = sp & 3;
-        const int64_t row0 = m0 + pg * 128 + pm * 32;
-        const int64_t left = rows - row0;
-        const int vr = left <= 0 ? 0 : left < 32 ? (int)left : 32;
-        constexpr int ES = RES ? 4 : 2;
-        // (K features: CLS rows dropped, the others move up -- infer.py:202 k[:, 1:] --: per-lane output row, one descriptor
-        //  over the whole output, 32-bit byte offsets checked by the launcher, dropped rows get an offset outside it)
-        const auto rs = EPI == VITTF_EPI_KFEAT
-            ? __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out), 0, (int)out_bytes, 0x00020000)
-            : __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out) + (vr ? (row0 * n + n0) * ES : 0), 0,
-                                                vr ? ((vr - 1) * n + PBN) * ES : 0, 0x00020000);
-        [[maybe_unused]] pu32x4_t xv[4];
-        if constexpr (RES) {
+    for (int sp = 0; sp < 8; ++sp) {
+      const int pg = sp >> 2, pm = sp & 3;
+      const int64_t row0 = m0 + pg * 128 + pm * 32;
+      const int64_t left = rows - row0;
+      const int vr = left <= 0 ? 0 : left < 32 ? (int)left : 32;
+      constexpr int ES = RES ? 4 : 2;
+      // (K features: CLS rows dropped, the others move up -- infer.py:202 k[:, 1:] --: per-lane output row, one descriptor
+      //  over the whole output, 32-bit byte offsets checked by the launcher, dropped rows get an offset outside it)
+      const auto rs = EPI == VITTF_EPI_KFEAT
+          ? __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out), 0, (int)out_bytes, 0x00020000)
+          : __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out) + (vr ? (row0 * n + n0) * ES : 0), 0,
+                                              vr ? ((vr - 1) * n + PBN) * ES : 0, 0x00020000);
+      [[maybe_unused]] pu32x4_t xv[4];
+      if constexpr (RES) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) xv[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((i * 8 + (tid >> 6)) * n + 4 * ch) * 4, 0, 0);
-        }
-        if (grp == pg) {
+        for (int i = 0; i < 4; ++i) xv[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((i * 8 + (tid >> 6)) * n + 4 * ch) * 4, 0, 0);
+      }
+      if (grp == pg) {
 #pragma unroll
-          for (int mi = 0; mi < 4; ++mi) {
-            if (mi != pm) continue;
+        for (int mi = 0; mi < 4; ++mi) {
+          if (mi != pm) continue;
 #pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
+          for (int ni = 0; ni < 2; ++ni) {
 #pragma unroll
-              for (int g = 0; g < 4; ++g) {
-                const int nl = wc * 64 + ni * 32 + 8 * g + 4 * h;
-                const float4 v = make_float4(acc[ni][mi][4 * g + 0], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
-                *reinterpret_cast<float4*>(stg + l31 * 1024 + (((nl >> 2) ^ l31) << 4)) = v;
-              }
+            for (int g = 0; g < 4; ++g) {
+              const int nl = wc * 64 + ni * 32 + 8 * g + 4 * h;
+              const float4 v = make_float4(acc[ni][mi][4 * g + 0], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
+              *reinterpret_cast<float4*>(stg + l31 * 1024 + (((nl >> 2) ^ l31) << 4)) = v;
             }
           }
         }
-        PP_BARRIER();
-        if constexpr (EPI == PP_EPI_QKV_FP8) {
-          // a thread owns 16 columns (four staged chunks) of ONE row of the part: 16 fp8 bytes = one 16-byte store.  A column
-          // tile lies inside ONE third (256 | n / 3): the whole tile is q, k or v.
-          const int rl = tid >> 4, c16 = tid & 15;
-          const int dm = n / 3, third = n0 / dm;
-          float v[16];
+      }
+      PP_BARRIER();
+      if constexpr (EPI == PP_EPI_QKV_FP8) {
+        // a thread owns 16 columns (four staged chunks) of ONE row of the part: 16 fp8 bytes = one 16-byte store.  A column
+        // tile lies inside ONE third (256 | n / 3): the whole tile is q, k or v.
+        const int rl = tid >> 4, c16 = tid & 15;
+        const int dm = n / 3, third = n0 / dm;
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float4 dv = *reinterpret_cast<const float4*>(stg + rl * 1024 + (((4 * c16 + j) ^ rl) << 4));
+          v[4 * j + 0] = dv.x * qs; v[4 * j + 1] = dv.y * qs; v[4 * j + 2] = dv.z * qs; v[4 * j + 3] = dv.w * qs;
+        }
+        float mx = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(v[e]));
+        const int64_t m = row0 + rl;
+        int64_t b = fb0;                                       // (slice of the row: at most one boundary inside a tile ...
+        if (tokens < PBM) b = m / tokens;                      //  ... unless the slices are tiny)
+        else if (m >= (fb0 + 1) * (int64_t)tokens) b = fb0 + 1;
+        const int tok = (int)(m - b * tokens);
+        if (third < 2) {
+          // this row's 32-wide block = the 16 + 16 columns of two neighbouring lanes: block maximum -> E8M0 scale -> e4m3 bytes
+          mx = fmaxf(mx, __shfl_xor(mx, 1));
+          const int ex = pp_scale_exp(mx);
+          const float inv = ldexpf(1.0f, -ex);
+          pu32x4_t pk8;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float4 dv = *reinterpret_cast<const float4*>(stg + rl * 1024 + (((4 * c16 + j) ^ rl) << 4));
-            v[4 * j + 0] = dv.x * qs; v[4 * j + 1] = dv.y * qs; v[4 * j + 2] = dv.z * qs; v[4 * j + 3] = dv.w * qs;
+            int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, 0, false);
+            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, w0, true);
+            pk8[j] = (unsigned)w0;
           }
-          float mx = 0.f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(v[e]));
-          const int64_t m = row0 + rl;
-          int64_t b = fb0;                                       // (slice of the row: at most one boundary inside a tile ...
-          if (tokens < PBM) b = m / tokens;                      //  ... unless the slices are tiny)
-          else if (m >= (fb0 + 1) * (int64_t)tokens) b = fb0 + 1;
-          const int tok = (int)(m - b * tokens);
-          if (third < 2) {
-            // this row's 32-wide block = the 16 + 16 columns of two neighbouring lanes: block maximum -> E8M0 scale -> e4m3 bytes
-            mx = fmaxf(mx, __shfl_xor(mx, 1));
-            const int ex = pp_scale_exp(mx);
-            const float inv = ldexpf(1.0f, -ex);
-            pu32x4_t pk8;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, 0, false);
-              w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, w0, true);
-              pk8[j] = (unsigned)w0;
-            }
-            const int col = (n0 - third * dm) + 16 * c16;                   // column inside the third: head 64 * hd + dim
-            const int hd = col >> 6, dim = col & 63;
-            // position of dim inside the 64-byte row: the matrix instruction's MX block b of a row is bytes 16 b .. 16 b + 15 of
-            // BOTH lane halves (k = 32 (byte >> 4) + 16 (lane >> 5) + (byte & 15): tools/micro/mfma_f8_scale_probe2), and the
-            // attention kernel's lane half hh reads bytes 32 hh .. 32 hh + 31: a row is stored as [d 0-15 | d 32-47 | d 16-31 | d 48-63]
-            const int pos = ((dim >> 4) & 1) * 32 + (dim >> 5) * 16;
-            const int64_t rowi = (b * f8.heads + hd) * f8.np + tok;
-            const bool ok = m < rows;
-            const int64_t total8 = (int64_t)f8.batch * f8.heads * f8.np;
-            const auto r8 = __builtin_amdgcn_make_buffer_rsrc(third == 0 ? f8.q8 : f8.k8, 0, (int)(unsigned)(total8 * 64), 0x00020000);
-            const auto rsc = __builtin_amdgcn_make_buffer_rsrc(third == 0 ? f8.qs : f8.ks, 0, (int)(unsigned)(total8 * 2), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(pk8, r8, ok ? (int)(unsigned)(rowi * 64 + pos) : (int)0x80000000u, 0, 0);      // (dropped rows: out of range without wrapping)
-            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(127 + ex), rsc, (ok && (c16 & 1) == 0) ? (int)(unsigned)(rowi * 2 + (dim >> 5)) : (int)0x80000000u, 0, 0);
-          } else {
-            // v: 16-bit values into the qkv buffer's v third; its absolute maximum per (slice, head) on the way out
-            if (tokens < PBM) {          // (tiny slices: a tile holds more than two of them -- one atomic per thread and row)
-              const int hd = ((n0 - 2 * dm) + 16 * c16) >> 6;
-              if (m < rows && mx > 0.f) atomicMax(f8.amax + (b * f8.heads + hd) * 3 + 2, __float_as_uint(mx));
-            } else if (m < rows) {
-              if (b == fb0) vmax_a = fmaxf(vmax_a, mx); else vmax_b = fmaxf(vmax_b, mx);
-            }
-            pu32x4_t p0, p1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { p0[e] = pack2_h16<DT>(v[2 * e], v[2 * e + 1]); p1[e] = pack2_h16<DT>(v[8 + 2 * e], v[8 + 2 * e + 1]); }
-            __builtin_amdgcn_raw_buffer_store_b128(p0, rs, (rl * n + 16 * c16) * 2, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(p1, rs, (rl * n + 16 * c16) * 2 + 16, 0, 0);
-          }
-        } else if constexpr (RES) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int rl = i * 8 + (tid >> 6);
-            const float4 d = *reinterpret_cast<const float4*>(stg + rl * 1024 + ((ch ^ rl) << 4));
-            float4 x = __builtin_bit_cast(float4, xv[i]);
-            x.x += d.x; x.y += d.y; x.z += d.z; x.w += d.w;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4_t, x), rs, (rl * n + 4 * ch) * 4, 0, 0);
-          }
+          const int col = (n0 - third * dm) + 16 * c16;                   // column inside the third: head 64 * hd + dim
+          const int hd = col >> 6, dim = col & 63;
+          // position of dim inside the 64-byte row: the matrix instruction's MX block b of a row is bytes 16 b .. 16 b + 15 of
+          // BOTH lane halves (k = 32 (byte >> 4) + 16 (lane >> 5) + (byte & 15): tools/micro/mfma_f8_scale_probe2), and the
+          // attention kernel's lane half hh reads bytes 32 hh .. 32 hh + 31: a row is stored as [d 0-15 | d 32-47 | d 16-31 | d 48-63]
+          const int pos = ((dim >> 4) & 1) * 32 + (dim >> 5) * 16;
+          const int64_t rowi = (b * f8.heads + hd) * f8.np + tok;
+          const bool ok = m < rows;
+          const int64_t total8 = (int64_t)f8.batch * f8.heads * f8.np;
+          const auto r8 = __builtin_amdgcn_make_buffer_rsrc(third == 0 ? f8.q8 : f8.k8, 0, (int)(unsigned)(total8 * 64), 0x00020000);
+          const auto rsc = __builtin_amdgcn_make_buffer_rsrc(third == 0 ? f8.qs : f8.ks, 0, (int)(unsigned)(total8 * 2), 0x00020000);
+          __builtin_amdgcn_raw_buffer_store_b128(pk8, r8, ok ? (int)(unsigned)(rowi * 64 + pos) : (int)0x80000000u, 0, 0);      // (dropped rows: out of range without wrapping)
+          __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(127 + ex), rsc, (ok && (c16 & 1) == 0) ? (int)(unsigned)(rowi * 2 + (dim >> 5)) : (int)0x80000000u, 0, 0);
         } else {
+          // v: 16-bit values into the qkv buffer's v third; its absolute maximum per (slice, head) on the way out
+          if (tokens < PBM) {          // (tiny slices: a tile holds more than two of them -- one atomic per thread and row)
+            const int hd = ((n0 - 2 * dm) + 16 * c16) >> 6;
+            if (m < rows && mx > 0.f) atomicMax(f8.amax + (b * f8.heads + hd) * 3 + 2, __float_as_uint(mx));
+          } else if (m < rows) {
+            if (b == fb0) vmax_a = fmaxf(vmax_a, mx); else vmax_b = fmaxf(vmax_b, mx);
+          }
+          pu32x4_t p0, p1;
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int rl = i * 16 + (tid >> 5);
-            const float4 d0 = *reinterpret_cast<const float4*>(stg + rl * 1024 + ((ch ^ rl) << 4));
-            const float4 d1 = *reinterpret_cast<const float4*>(stg + rl * 1024 + (((ch + 1) ^ rl) << 4));
-            float v[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+          for (int e = 0; e < 4; ++e) { p0[e] = pack2_h16<DT>(v[2 * e], v[2 * e + 1]); p1[e] = pack2_h16<DT>(v[8 + 2 * e], v[8 + 2 * e + 1]); }
+          __builtin_amdgcn_raw_buffer_store_b128(p0, rs, (rl * n + 16 * c16) * 2, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(p1, rs, (rl * n + 16 * c16) * 2 + 16, 0, 0);
+        }
+      } else if constexpr (RES) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              if constexpr (EPI == VITTF_EPI_BIAS_GELU) v[e] = gelu_poly(v[e]);
-              if constexpr (EPI == VITTF_EPI_BIAS_QKV) v[e] *= qs;   // the q third: softmax scale and exp -> exp2 base change
-            }
-            pu32x4_t pk;
-            if constexpr (EPI == PP_EPI_KFEAT_PARTS) {
+        for (int i = 0; i < 4; ++i) {
+          const int rl = i * 8 + (tid >> 6);
+          const float4 d = *reinterpret_cast<const float4*>(stg + rl * 1024 + ((ch ^ rl) << 4));
+          float4 x = __builtin_bit_cast(float4, xv[i]);
+          x.x += d.x; x.y += d.y; x.z += d.z; x.w += d.w;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4_t, x), rs, (rl * n + 4 * ch) * 4, 0, 0);
+        }
+      } else {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
-              const int third = n0 / kp.d;
-              const auto rp = __builtin_amdgcn_make_buffer_rsrc(kp.out[third], 0, (int)kp.bytes, 0x00020000);
-              const int64_t m = row0 + rl;
-              const int64_t b = m / tokens;
-              const int tok = (int)(m - b * tokens);
-              const int64_t orow = b * (tokens - 1) + tok - 1;
-              if (m < rows && tok != 0)        // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
-                __builtin_amdgcn_raw_buffer_store_b128(pk, rp, (int)(unsigned)((orow * kp.d + (n0 - third * kp.d) + 4 * ch) * 2),
-                                                       0, PV_ST_AUX);
-            } else if constexpr (EPI == VITTF_EPI_KFEAT) {
+        for (int i = 0; i < 2; ++i) {
+          const int rl = i * 16 + (tid >> 5);
+          const float4 d0 = *reinterpret_cast<const float4*>(stg + rl * 1024 + ((ch ^ rl) << 4));
+          const float4 d1 = *reinterpret_cast<const float4*>(stg + rl * 1024 + (((ch + 1) ^ rl) << 4));
+          float v[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
 #pragma unroll
-              for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
-              const int64_t m = row0 + rl;
-              const int64_t b = m / tokens;
-              const int tok = (int)(m - b * tokens);
-              const int64_t orow = b * (tokens - 1) + tok - 1;
-              const unsigned off = (m < rows && tok != 0) ? (unsigned)((orow * n + n0 + 4 * ch) * 2) : 0x80000000u;      // (dropped rows: an offset whose 16 bytes cannot wrap into the buffer)
-              __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (int)off, 0, PV_ST_AUX);
-            } else {
+          for (int e = 0; e < 8; ++e) {
+            if constexpr (EPI == VITTF_EPI_BIAS_GELU) v[e] = gelu_poly(v[e]);
+            if constexpr (EPI == VITTF_EPI_BIAS_QKV) v[e] *= qs;   // the q third: softmax scale and exp -> exp2 base change
+          }
+          pu32x4_t pk;
+          if constexpr (EPI == PP_EPI_KFEAT_PARTS) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<DT>(v[2 * e], v[2 * e + 1]);
-              __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (rl * n + 4 * ch) * 2, 0, PV_ST_AUX);
-            }
+            for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
+            const int third = n0 / kp.d;
+            const auto rp = __builtin_amdgcn_make_buffer_rsrc(kp.out[third], 0, (int)kp.bytes, 0x00020000);
+            const int64_t m = row0 + rl;
+            const int64_t b = m / tokens;
+            const int tok = (int)(m - b * tokens);
+            const int64_t orow = b * (tokens - 1) + tok - 1;
+            if (m < rows && tok != 0)        // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
+              __builtin_amdgcn_raw_buffer_store_b128(pk, rp, (int)(unsigned)((orow * kp.d + (n0 - third * kp.d) + 4 * ch) * 2),
+                                                     0, PP_STORE_AUX);
+          } else if constexpr (EPI == VITTF_EPI_KFEAT) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
+            const int64_t m = row0 + rl;
+            const int64_t b = m / tokens;
+            const int tok = (int)(m - b * tokens);
+            const int64_t orow = b * (tokens - 1) + tok - 1;
+            const unsigned off = (m < rows && tok != 0) ? (unsigned)((orow * n + n0 + 4 * ch) * 2) : 0x80000000u;      // (dropped rows: an offset whose 16 bytes cannot wrap into the buffer)
+            __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (int)off, 0, PP_STORE_AUX);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<DT>(v[2 * e], v[2 * e + 1]);
+            __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (rl * n + 4 * ch) * 2, 0, PP_STORE_AUX);
           }
         }
-        PP_BARRIER();
       }
-      if constexpr (EPI == PP_EPI_KFEAT_PARTS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (predicated stores: see PpParts)
-      if constexpr (EPI == PP_EPI_QKV_FP8) {
-        const int dm = n / 3;
-        if (n0 / dm == 2) {
-          // the 4 lanes that share a head (16 columns each), then the wave's four rows: one atomic per head, slice and wave
+      PP_BARRIER();
+    }
+    if constexpr (EPI == PP_EPI_KFEAT_PARTS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (predicated stores: see PpParts)
+    if constexpr (EPI == PP_EPI_QKV_FP8) {
+      const int dm = n / 3;
+      if (n0 / dm == 2) {
+        // the 4 lanes that share a head (16 columns each), then the wave's four rows: one atomic per head, slice and wave
 #pragma unroll
-          for (int off = 1; off <= 2; off <<= 1) { vmax_a = fmaxf(vmax_a, __shfl_xor(vmax_a, off)); vmax_b = fmaxf(vmax_b, __shfl_xor(vmax_b, off)); }
+        for (int off = 1; off <= 2; off <<= 1) { vmax_a = fmaxf(vmax_a, __shfl_xor(vmax_a, off)); vmax_b = fmaxf(vmax_b, __shfl_xor(vmax_b, off)); }
 #pragma unroll
-          for (int off = 16; off <= 32; off <<= 1) { vmax_a = fmaxf(vmax_a, __shfl_xor(vmax_a, off)); vmax_b = fmaxf(vmax_b, __shfl_xor(vmax_b, off)); }
-          if ((lane & 51) == 0) {                // lanes 0, 4, 8, 12
-            const int hd = ((n0 - 2 * dm) >> 6) + (lane >> 2);
-            const int64_t b0 = m0 / tokens;
-            if (vmax_a > 0.f) atomicMax(f8.amax + (b0 * f8.heads + hd) * 3 + 2, __float_as_uint(vmax_a));
-            if (vmax_b > 0.f && b0 + 1 < f8.batch) atomicMax(f8.amax + ((b0 + 1) * f8.heads + hd) * 3 + 2, __float_as_uint(vmax_b));
-          }
+        for (int off = 16; off <= 32; off <<= 1) { vmax_a = fmaxf(vmax_a, __shfl_xor(vmax_a, off)); vmax_b = fmaxf(vmax_b, __shfl_xor(vmax_b, off)); }
+        if ((lane & 51) == 0) {                // lanes 0, 4, 8, 12
+          const int hd = ((n0 - 2 * dm) >> 6) + (lane >> 2);
+          const int64_t b0 = m0 / tokens;
+          if (vmax_a > 0.f) atomicMax(f8.amax + (b0 * f8.heads + hd) * 3 + 2, __float_as_uint(vmax_a));
+          if (vmax_b > 0.f && b0 + 1 < f8.batch) atomicMax(f8.amax + ((b0 + 1) * f8.heads + hd) * 3 + 2, __float_as_uint(vmax_b));
         }
       }
     }
@@ -502,14 +482,7 @@ int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_
 
 }  // namespace
 
-#ifdef PP_STANDALONE      // tools/pp_variants.sh builds this file alone
-void vittf_note_kernel(int, const char*) {}
-#endif
-
 // 1 = shape not covered (the caller falls back to gemm.hip's 128 x 128 tiles)
-#ifdef PP_STANDALONE
-extern "C"
-#endif
 int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
                   int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st) {
   if (k < 768 || k % (2 * PBK) != 0 || n % PBN != 0) return 1;
@@ -551,7 +524,6 @@ int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, i
   return rc;
 }
 
-#ifndef PP_STANDALONE
 void vittf_fp8_ws_pointers(void* ws, int32_t batch, int32_t tokens, int32_t heads, unsigned** amax, unsigned char** q8,
                            unsigned char** k8, unsigned char** qs, unsigned char** ks, int32_t* np);   // attention_fp8.hip
 
@@ -597,4 +569,3 @@ extern "C" int vittf_gemm_qkv_fp8(const void* a, const void* w, const float* bia
   if (dtype == VITTF_BF16) return launch_pp<VITTF_BF16>(a, w, bias, qkv_out, rows, n, k, PP_EPI_QKV_FP8, tokens, st, f8);
   return launch_pp<VITTF_FP16>(a, w, bias, qkv_out, rows, n, k, PP_EPI_QKV_FP8, tokens, st, f8);
 }
-#endif

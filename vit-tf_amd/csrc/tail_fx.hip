@@ -20,12 +20,11 @@
 // hidden unit, the next tile's attention-output fragments and residual chunks F -> X at the tile boundary.
 //
 // The weights arrive as ONE stream of 24 KB steps through an LDS-DMA ring (packed by the host in consumption order and LDS
-// layout, weights.pack_tail_fx_weights): 24 projection steps [ - | Wp k step p of all 12 output tiles ] = 12 MFMAs of X, then
-// 100 main steps [ W1(u) k half | W2(u - 2) output-tile half ] = 12 MFMAs of F + 12 MFMAs of X, F two hidden units ahead.
-// One bare barrier per step, counted vmcnt (X).  Measured design points: profiles/r05a_tail_fx_pricing.txt.
+// layout, weights.pack_block_tail_weights): 12 projection steps [ Wp k steps 2 p, 2 p + 1 of all 12 output tiles ] = 24 MFMAs
+// of X, then 100 main steps [ W1(u) k half | W2(u - 2) output-tile half ] = 12 MFMAs of F + 12 MFMAs of X, F two hidden units
+// ahead.  One bare barrier per step, counted vmcnt (X).  Measured design points: profiles/r05a_tail_fx_pricing.txt.
 #include "vittf_common.h"
 
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -36,19 +35,8 @@ constexpr int SB = 24576, HB = SB / 2;       // bytes of one ring step / of one 
 constexpr int PSTEPS = D / 32;               // projection steps in front (X: 24 MFMAs each, two k steps of all output tiles)
 constexpr int LAG = 4;                       // main steps between a half of fc1(u) and the same half of fc2(u)
 constexpr int MSTEPS = 2 * UNITS + LAG;      // main steps of a row tile
-#ifndef FX_VARIANT
-#define FX_VARIANT 0
-#endif
-#ifndef FX_NSLOT
-#define FX_NSLOT 4
-#endif
-// timing-only builds (tools/fx_variants.sh; never in libvittf.so): 1 = main phase only (no tile boundary), 2 = no GELU
-// arithmetic, 4 = no LDS-DMA inside the steps, 8 = no fragment refills, 16 = stamps, 32 = steps without their barrier,
-// 64 = no raised priority for the F waves
-constexpr bool V_MAIN_ONLY = FX_VARIANT & 1, V_NO_GELU = FX_VARIANT & 2, V_NO_DMA = FX_VARIANT & 4, V_NO_REFILL = FX_VARIANT & 8,
-               V_NO_BARRIER = FX_VARIANT & 32, V_NO_PRIO = FX_VARIANT & 64;
-constexpr int NSEQ = V_MAIN_ONLY ? MSTEPS : PSTEPS + MSTEPS;
-constexpr int NSLOT = FX_NSLOT, AHEAD = NSLOT - 1;
+constexpr int NSEQ = PSTEPS + MSTEPS;        // ring steps of a row tile
+constexpr int NSLOT = 4, AHEAD = NSLOT - 1;
 constexpr int PIECES = SB / 1024 / 4;        // LDS-DMA pieces per X wave and step
 constexpr int WAIT0 = (AHEAD - 2) * PIECES;  // pieces of an X wave that may be in flight when a step starts
 constexpr int NF = 4;                        // weight fragments in flight per wave
@@ -86,21 +74,6 @@ struct Ring {                  // where the weight stream stands (wave-uniform)
 __device__ __forceinline__ s16x8_t ld_frag(const unsigned (&base)[4], int f) {
   return *(lds_frag_ptr)(base[f & 3] + (f >> 2) * 4096);
 }
-
-#if FX_VARIANT & 16
-__device__ unsigned long long g_fx_stamps[4 /*workgroups*/][4 /*tiles*/][8 /*waves*/][8];
-__device__ unsigned g_fx_hwid[8];
-#define FX_STAMP(k)                                                                                           \
-  do {                                                                                                        \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_[k])::"memory");                       \
-    if (k == 7 && blockIdx.x < 4 && tile_no < 4 && (threadIdx.x & 63) == 0) {                                 \
-      _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_)                                                        \
-        g_fx_stamps[blockIdx.x][tile_no][threadIdx.x >> 6][q_] = stamp_[q_];                                  \
-    }                                                                                                         \
-  } while (0)
-#else
-#define FX_STAMP(k)
-#endif
 
 // an LDS-DMA piece that leaves M0 pointing at its destination (hipcc keeps nothing in M0 in this kernel:
 // tests/test_host_cpu.py checks the disassembly for that)
@@ -140,21 +113,18 @@ __device__ __forceinline__ float gelu_c(const Gelu3& s) {
 template <int WAITN, bool LGKM = false>
 __device__ __forceinline__ void x_wait() {
   static_assert(WAITN <= 63, "vmcnt");
-  if constexpr (V_NO_BARRIER) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(V_NO_DMA || WAITN < 0 ? 0 : WAITN) : "memory");
-  } else if constexpr (WAITN < 0) {
+  if constexpr (WAITN < 0) {
     if constexpr (LGKM) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_barrier" ::: "memory");
   } else if constexpr (LGKM) {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(V_NO_DMA ? 0 : WAITN) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(WAITN) : "memory");
   } else {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(V_NO_DMA ? 0 : WAITN) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(WAITN) : "memory");
   }
 }
 // F (no LDS-DMA of its own: the X waves' waits + the barrier publish the ring), and both roles in the rounds without a ring step
 template <bool LGKM = false>
 __device__ __forceinline__ void sync_wait() {
-  if constexpr (V_NO_BARRIER) return;
   if constexpr (LGKM) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   else asm volatile("s_barrier" ::: "memory");
 }
@@ -167,7 +137,6 @@ __device__ __forceinline__ void ring_advance(Ring& st) {
 }
 // piece i (0 .. 5) of this X wave for the step AHEAD, into the slot the barrier of this step has freed
 __device__ __forceinline__ void ring_piece(const Ring& st, int i, int g_next, int slot_free) {
-  if (V_NO_DMA) return;
   const int off = st.src0 + i * 1024;
   lds_dma16_keep(st.rsrc, st.dma_dst + slot_free * SB + off, (int)((threadIdx.x & 63) * 16), g_next * SB + off);
 }
@@ -185,7 +154,7 @@ __device__ __forceinline__ void rotate_bases(const Ring& st, unsigned (&base)[4]
 template <bool LAST, bool DMA, int NM = 12>
 __device__ __forceinline__ void ring_gap(const Ring& st, unsigned (&base)[4], s16x8_t (&wf)[NF], int j, int g_next, int slot_free) {
   if (j == NM - NF && !LAST) rotate_bases(st, base);
-  if (!V_NO_REFILL && !(LAST && j >= NM - NF)) wf[j % NF] = ld_frag(base, (j + NF) % NM);
+  if (!(LAST && j >= NM - NF)) wf[j % NF] = ld_frag(base, (j + NF) % NM);
   if (DMA && j % (NM / PIECES) == NM / PIECES - 1) ring_piece(st, j / (NM / PIECES), g_next, slot_free);
 }
 
@@ -213,9 +182,7 @@ __device__ __forceinline__ void f_step(Ring& st, unsigned (&base)[4], s16x8_t (&
     ring_gap<LAST, false>(st, base, wf, j, 0, 0);
     if constexpr (GELU) {
       const int r = 8 * KH + 2 * (j / 3);
-      if (V_NO_GELU) {
-        if (j % 3 == 2) pk[j / 3] = pack2_h16<DT>(gprev[r], gprev[r + 1]);
-      } else if (j % 3 == 0) {
+      if (j % 3 == 0) {
         gelu_a(s0, gprev[r]); gelu_a(s1, gprev[r + 1]);
       } else if (j % 3 == 1) {
         gelu_b(s0); gelu_b(s1);
@@ -319,8 +286,6 @@ template <typename T> __device__ __forceinline__ T* uni_ptr(T* p) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p)) + (nrows ? first : 0) * row_bytes, 0, \
                                              nrows * row_bytes, 0x00020000);                                              \
   };                                                                                                                      \
-  [[maybe_unused]] int tile_no = -1;                                                                                      \
-  [[maybe_unused]] unsigned long long stamp_[8] = {};                                                                     \
   (void)abuf; (void)x; (void)hout; (void)tile_ctr; (void)ln_eps; (void)ntiles; (void)l31; (void)aoff0; (void)nxt; (void)cst4; (void)tile_rsrc
 
 // =============================================== F: the 16-bit rows ===============================================
@@ -328,7 +293,7 @@ template <int DT>
 __device__ __attribute__((noinline)) void run_f(Ctx c) {
   FX_ROLE_ENV;
   // =============================================== F: the 16-bit rows ===============================================
-  if (!V_NO_PRIO) asm volatile("s_setprio 3");     // its GELU pieces go in front of the X wave's MFMA waiting for the pipe
+  asm volatile("s_setprio 3");                     // its GELU pieces go in front of the X wave's MFMA waiting for the pipe
   unsigned pbl = pbuf + lane * 16;                 // lane-linear 16-byte slots of the pair buffer
   asm volatile("" : "+v"(pbl));
   // The next tile's rows, as loaded (eight lanes per row, 128-byte runs): fb[4 cg + i] = a[row 8 i + lane / 8][64 cg + 8 (lane % 8) ..]
@@ -369,12 +334,10 @@ __device__ __attribute__((noinline)) void run_f(Ctx c) {
     for (int c = 0; c < 6; ++c) load_chunk(c);
     put_a(0);
   };
-  if constexpr (!V_MAIN_ONLY) fetch_rows(tile);
+  fetch_rows(tile);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   while (true) {
-    ++tile_no;
-    FX_STAMP(0);
     unsigned next_v = 0;
     if (tid == 256) next_v = atomicAdd(tile_ctr, 1u);
     unsigned base[4];
@@ -388,40 +351,31 @@ __device__ __attribute__((noinline)) void run_f(Ctx c) {
         bias_c[4 * q + 0] = bv[0]; bias_c[4 * q + 1] = bv[1]; bias_c[4 * q + 2] = bv[2]; bias_c[4 * q + 3] = bv[3];
       }
     };
-    if constexpr (V_MAIN_ONLY) {      // (timing: any data will do)
-      const auto rs = tile_rsrc(abuf, tile, D * 2);
+    // ---- projection steps (k steps 2 p, 2 p + 1): the X wave computes; column group cg of a goes over during step 2 cg - 2
+    //      (read from step 2 cg - 1 on; its slots were read last during step 2 cg - 4), and the registers it leaves take the
+    //      next residual chunk
 #pragma unroll
-      for (int s = 0; s < D / 16; ++s) hf[s] = __builtin_bit_cast(s16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rs, (rb * 32 + l31) * (D * 2) + 16 * h, 32 * s, 0));
+    for (int p = 0; p < PSTEPS; ++p) {
+      sync_wait<true>();
+      if (p % 2 == 0 && p / 2 + 1 < 6) put_a(p / 2 + 1);
+      if (p == 0) load_chunk(6);
+      if (p % 2 == 1 && p / 2 < 5) load_chunk(7 + p / 2);
+      if (p == PSTEPS - 1) put_chunk(0);
+      ring_advance(st);
     }
-    if constexpr (!V_MAIN_ONLY) {
-      // ---- projection steps (k steps 2 p, 2 p + 1): the X wave computes; column group cg of a goes over during step 2 cg - 2
-      //      (read from step 2 cg - 1 on; its slots were read last during step 2 cg - 4), and the registers it leaves take the
-      //      next residual chunk
+    // ---- residual rounds: chunk r is in half r & 1 (written during the round before), chunk r + 1 goes into the other half
 #pragma unroll
-      for (int p = 0; p < PSTEPS; ++p) {
-        sync_wait<true>();
-        if (p % 2 == 0 && p / 2 + 1 < 6) put_a(p / 2 + 1);
-        if (p == 0) load_chunk(6);
-        if (p % 2 == 1 && p / 2 < 5) load_chunk(7 + p / 2);
-        if (p == PSTEPS - 1) put_chunk(0);
-        ring_advance(st);
-      }
-      FX_STAMP(1);
-      // ---- residual rounds: chunk r is in half r & 1 (written during the round before), chunk r + 1 goes into the other half
-#pragma unroll
-      for (int r = 0; r < 12; ++r) {
-        sync_wait<true>();
-        if (r + 1 < 12) put_chunk(r + 1);
-      }
-      // ---- norm2's output, two k steps per round from half r & 1
-#pragma unroll
-      for (int r = 0; r < 12; ++r) {
-        sync_wait<true>();
-        hf[2 * r] = *(lds_frag_ptr)(pbl + (r & 1) * PBH);
-        hf[2 * r + 1] = *(lds_frag_ptr)(pbl + (r & 1) * PBH + 1024);
-      }
+    for (int r = 0; r < 12; ++r) {
+      sync_wait<true>();
+      if (r + 1 < 12) put_chunk(r + 1);
     }
-    FX_STAMP(2);
+    // ---- norm2's output, two k steps per round from half r & 1
+#pragma unroll
+    for (int r = 0; r < 12; ++r) {
+      sync_wait<true>();
+      hf[2 * r] = *(lds_frag_ptr)(pbl + (r & 1) * PBH);
+      hf[2 * r + 1] = *(lds_frag_ptr)(pbl + (r & 1) * PBH + 1024);
+    }
     // ---- main steps
     f32x16_t ga, gb = {};
     u32x4_t pk0 = {}, pk1 = {};
@@ -453,7 +407,6 @@ __device__ __attribute__((noinline)) void run_f(Ctx c) {
       f_step<DT, 1, true, false, false>(st, base, wf, hf, ga, bias_c, gb, pk1);
       put_gf(1);
     }
-    FX_STAMP(3);
     load_bias(C_B1 + 32 * (UNITS - 1));
     f_step<DT, 0, true, false, true>(st, base, wf, hf, gb, bias_c, ga, pk0);            // fc1(47) | gelu(46) -> half 0
     f_step<DT, 1, true, true, false>(st, base, wf, hf, gb, bias_c, ga, pk1);
@@ -463,7 +416,7 @@ __device__ __attribute__((noinline)) void run_f(Ctx c) {
     ring_advance(st);
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      const float v0 = V_NO_GELU ? gb[r] : gelu_poly(gb[r]), v1 = V_NO_GELU ? gb[r + 1] : gelu_poly(gb[r + 1]);
+      const float v0 = gelu_poly(gb[r]), v1 = gelu_poly(gb[r + 1]);
       const unsigned w = pack2_h16<DT>(v0, v1);
       if (r < 8) pk0[r >> 1] = w; else pk1[(r - 8) >> 1] = w;
     }
@@ -471,15 +424,13 @@ __device__ __attribute__((noinline)) void run_f(Ctx c) {
     sync_wait<true>(); ring_advance(st);
     sync_wait(); ring_advance(st);
     sync_wait(); ring_advance(st);
-    FX_STAMP(4);
     // ---- drain; the next tile's rows go on their way while the X wave runs its epilogue
     if (tid == 256) *(lds_u32_ptr)nxt = next_v;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const int next = __builtin_amdgcn_readfirstlane((int)*(lds_u32_ptr)nxt);
-    FX_STAMP(5); FX_STAMP(6); FX_STAMP(7);
     if (next >= ntiles) break;
     tile = next;
-    if constexpr (!V_MAIN_ONLY) fetch_rows(tile);
+    fetch_rows(tile);
   }
 }
 
@@ -493,16 +444,10 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
   __syncthreads();
   s16x8_t wf[NF];
   f32x16_t xacc[D / 32];
-  if constexpr (V_MAIN_ONLY) {
-#pragma unroll
-    for (int ot = 0; ot < D / 32; ++ot) xacc[ot] = f32x16_t{};
-  }
   while (true) {
-    ++tile_no;
-    FX_STAMP(0);
     int ln = lane;             // (opaque: addresses are recomputed per phase, a few VALU, not carried -- spilled -- across the steps)
     asm volatile("" : "+v"(ln));
-    if constexpr (!V_MAIN_ONLY) {
+    {      // (a scope of its own, like the epilogue's: both compute a LayerNorm under the same names)
       // ---- x' = a . Wp^T + bp (+ x below): every accumulator starts from its bias tile (register r of lane half h = constant
       //      at + (r & 3) + 8 (r >> 2) + 4 h), one k step of all 12 output tiles per step
 #pragma unroll
@@ -531,7 +476,6 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
       }
       p_step<DT, WAIT0, false, false>(st, base, wf, xacc, aa, ab, af_rd + af_off(2 * PSTEPS - 2), af_rd + af_off(2 * PSTEPS - 1));
       p_step<DT, WAIT0, false, true>(st, base, wf, xacc, ab, aa, 0, 0);
-      FX_STAMP(1);
       // ---- + x: residual chunk r (32 columns) from half r & 1 of the pair buffer, a row per lane
       const unsigned ch_rd = pbuf + (ln & 31) * STG_ROW + 16 * (ln >> 5);
 #pragma unroll
@@ -599,7 +543,6 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
         sync_wait<true>();
       }
     }
-    FX_STAMP(2);
     // ---- main steps: 0 .. 3 idle (the F wave is two hidden units ahead)
     s16x8_t gf[2];
     x_idle_step<WAIT0>(st); x_idle_step<WAIT0>(st); x_idle_step<WAIT0>(st);
@@ -621,17 +564,15 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
       x_step<DT, 0, false>(st, base, wf, xacc, gf, gfa + PBH);         // fc2(u + 1)
       x_step<DT, 1, false>(st, base, wf, xacc, gf, gfa + PBH);
     }
-    FX_STAMP(3);
     x_step<DT, 0, false>(st, base, wf, xacc, gf, gfa);                 // fc2(46)
     x_step<DT, 1, false>(st, base, wf, xacc, gf, gfa);
     x_step<DT, 0, false>(st, base, wf, xacc, gf, gfa + PBH);           // fc2(47)
     x_step<DT, 1, true>(st, base, wf, xacc, gf, gfa + PBH);
-    FX_STAMP(4);
     // ---- drain: everything this wave has requested has landed (the first AHEAD steps of the next tile: its first steps wait
     //      for nothing but their barriers, which gives the stores below until then), and the next tile is known
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     const int next = __builtin_amdgcn_readfirstlane((int)*(lds_u32_ptr)nxt);
-    if constexpr (!V_MAIN_ONLY) {
+    {
       // ---- epilogue: x[row][col .. col + 3] = acc + b2, lane owns row m, columns 32 ot + 8 g + 4 h + {0 .. 3}, through the
       //      first half of the pair buffer (written a row per lane, read back eight lanes per row, stored in 128-byte runs);
       //      then the LayerNorm of the new row from the same registers, h out the same way
@@ -680,7 +621,6 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      FX_STAMP(5);
       if (hout) {
         {
           const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
@@ -698,7 +638,6 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
           const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(q), __float_as_uint(q), false, false);
           q = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
         }
-        FX_STAMP(6);
         const float rstd = 1.0f / sqrtf(q / (float)D + ln_eps);
         float mean_p = mean;
         asm volatile("" : "+v"(mean_p));
@@ -737,17 +676,8 @@ __device__ __attribute__((noinline)) void run_x(Ctx c) {
         }
       }
     }
-    FX_STAMP(7);
     if (next >= ntiles) break;
     tile = next;
-  }
-  if (V_MAIN_ONLY && x) {      // (timing build: keep the accumulators alive)
-    float s = 0.f;
-#pragma unroll
-    for (int ot = 0; ot < D / 32; ++ot)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s += xacc[ot][r];
-    if (s == 12345.678f) x[tid] = s;
   }
 }
 
@@ -788,13 +718,6 @@ __global__ __launch_bounds__(512, 1) void tail_fx_kernel(const unsigned short* _
       for (int i = 0; i < PIECES; ++i)
         lds_dma16(rsrc, lds0 + wave * (PIECES * 1024) + u * SB + i * 1024, lane * 16, u * SB + wave * (PIECES * 1024) + i * 1024);
   }
-#if FX_VARIANT & 16
-  if (blockIdx.x == 0 && lane == 0) {
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    g_fx_hwid[wave] = hw;
-  }
-#endif
   const Ctx c = {abuf, wpk, x, hout, tile_ctr, rows, ln_eps, ntiles, tile, lds0};
   if (wave >= 4) run_f<DT>(c);
   else run_x<DT>(c);
@@ -802,17 +725,6 @@ __global__ __launch_bounds__(512, 1) void tail_fx_kernel(const unsigned short* _
 }
 
 }  // namespace
-
-#if FX_VARIANT & 16
-extern "C" int vittf_fx_stamps(unsigned long long* out, unsigned* hwid) {
-  if (hipMemcpyFromSymbol(hwid, HIP_SYMBOL(g_fx_hwid), sizeof(g_fx_hwid)) != hipSuccess) return -1;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fx_stamps), sizeof(g_fx_stamps)) == hipSuccess ? 0 : -1;
-}
-#endif
-
-#ifdef FX_STANDALONE      // tools/fx_variants.sh builds this file alone
-void vittf_note_kernel(int, const char*) {}
-#endif
 
 extern "C" size_t vittf_block_tail_workspace_bytes(void) { return sizeof(unsigned); }
 
@@ -831,10 +743,7 @@ extern "C" int vittf_block_tail(const void* attn_out, const void* w_packed, cons
   // one persistent workgroup per CU of the device this call runs on (asked per call: no state is kept between calls)
   const int cus = vittf_current_cus();
   if (cus <= 0) return VITTF_ERR_NO_DEVICE;
-  unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
-#ifdef FX_STANDALONE      // (timing builds: the same tiles per workgroup on fewer CUs tell a bandwidth bound from a latency chain)
-  if (const char* e = getenv("VITTF_FX_GRID")) grid = (unsigned)atoi(e) < grid ? (unsigned)atoi(e) : grid;
-#endif
+  const unsigned grid = (unsigned)(tiles < cus ? tiles : cus);
   hipStream_t st = (hipStream_t)stream;
   // the tile counter is the caller's memory (launches on one stream are serialised; two streams bring two counters)
   unsigned* ctr = (unsigned*)tile_counter;

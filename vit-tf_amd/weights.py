@@ -270,7 +270,7 @@ def pack_row_images(w):
 
 def norm2_register_order():
     """Column of x held at fc1 input position 16 s + 8 h + e when norm2 is computed in the block-tail kernel's accumulator
-    registers (csrc/mlp.hip): 32 (s >> 1) + 16 (s & 1) + 8 (e >> 2) + 4 h + (e & 3)."""
+    registers (csrc/tail_fx.hip): 32 (s >> 1) + 16 (s & 1) + 8 (e >> 2) + 4 h + (e & 3)."""
     p = torch.arange(384)
     s_, h, e = p >> 4, (p >> 3) & 1, p & 7
     return 32 * (s_ >> 1) + 16 * (s_ & 1) + 8 * (e >> 2) + 4 * h + (e & 3)
