@@ -69,6 +69,7 @@ enum {
   VITTF_CFG_UNSCALED_Q = 2,        /* q as the model produces it + the online-maximum attention kernel (vittf_attention(.., 0)) */
   VITTF_CFG_FP8_HEAD_SCALES = 4    /* fp8 attention with one scale per (slice, head) (absmax + quantise launches) instead of row scales */
 };
+#define VITTF_MAX_REGISTER_TOKENS 8 /* most register tokens (DINOv2 _reg models carry 4) the *_reg entry points take */
 #define VITTF_TAIL_STEPS 112       /* 24 KB steps of one block in vittf_vit_weights.tail_packed */
 
 /* All weights live in HBM for the lifetime of the engine (about 43 MB for ViT-S).  Per-layer tensors
@@ -124,7 +125,7 @@ typedef struct vittf_slice_view {
 size_t vittf_minmax_workspace_bytes(void);
 int vittf_volume_minmax(const float* vol, int64_t n, float* out_minmax, void* ws, size_t ws_bytes, void* stream);
 
-/* Bytes of workspace for a forward over `batch` slices of `tokens` = f0*f1 + 1 tokens. */
+/* Bytes of workspace for a forward over `batch` slices of `tokens` = f0*f1 + 1 tokens (+ n_reg for vittf_vit_qkv_features_reg). */
 size_t vittf_vit_workspace_bytes(const vittf_vit_config* cfg, int32_t batch, int32_t tokens);
 
 /* The ViT leg of compute_qkv (infer.py:173-177 + the hooked K third, infer.py:133-135, 189-203):
@@ -148,6 +149,17 @@ int vittf_vit_k_features(const vittf_vit_config* cfg, const vittf_vit_weights* w
 int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
                            const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
                            uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream);
+
+/* vittf_vit_qkv_features for a model with n_reg register tokens (DINOv2 dinov2_vit{s,b,l}14_reg: 4; 0 .. VITTF_MAX_REGISTER_TOKENS):
+ * the token rows of a slice are [CLS, reg_0 .. reg_{n_reg-1}, patch_0 ..], tokens = f0*f1 + 1 + n_reg (the workspace query
+ * takes that number).  reg_rows: fp32 [n_reg][D], the checkpoint's register_tokens; they get no position embedding, take part
+ * in the attention of every block and are dropped together with CLS: the outputs keep vittf_vit_k_features' layout, f0*f1 rows
+ * per slice.  The 32-bit offset limit applies to batch * tokens.  n_reg = 0 (reg_rows ignored) is vittf_vit_qkv_features, bit
+ * for bit.  [host] cfg, w, pos, view are host structs holding device pointers. */
+int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                               const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                               const float* reg_rows, int32_t n_reg, uint16_t* q_out, uint16_t* k_out, uint16_t* v_out,
+                               void* ws, size_t ws_bytes, void* stream);
 
 /* Optional timing of the launches inside vittf_vit_k_features and vittf_similarity, by kernel class, with HIP events recorded on
  * the caller's stream (what bench.py's roofline leg reads).  Process-global, off by default, not thread-safe:
@@ -181,6 +193,13 @@ const char* vittf_profiler_kernel_name(int32_t kernel_class);
 int vittf_patch_embed(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
                       const vittf_slice_view* view, int32_t slice0, int32_t batch, float* tokens_out, void* stream);
 
+/* vittf_patch_embed with n_reg register rows behind CLS: tokens[b][0] = cls+pos0 ; tokens[b][1+r] = reg_rows[r] (bit for bit) ;
+ * tokens[b][1+n_reg+p] = patch_embed(slice slice0+b)[p] + pos[p]   -> fp32 [batch][f0*f1 + 1 + n_reg][D].  A row's bits do not
+ * depend on n_reg or on the batching. */
+int vittf_patch_embed_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                          const vittf_slice_view* view, int32_t slice0, int32_t batch, const float* reg_rows, int32_t n_reg,
+                          float* tokens_out, void* stream);
+
 /* y = LayerNorm(x) * g + b, x fp32 [rows][D] -> y h16 [rows][D]  (nn.LayerNorm, biased variance) */
 int vittf_layernorm(const float* x, const float* g, const float* b, void* y, int64_t rows, int32_t d,
                     float eps, int32_t dtype, void* stream);
@@ -210,6 +229,13 @@ int vittf_gemm(const void* a, const void* w, const float* bias, void* out, int64
 int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
                            int32_t tokens, int32_t part_mask, void* q_out, void* k_out, void* v_out, int32_t dtype,
                            void* stream);
+
+/* vittf_gemm_kfeat_parts with n_reg register rows behind CLS: rows whose (row % tokens) <= n_reg are dropped, the others go to
+ * out[(row/tokens)*(tokens-1-n_reg) + row%tokens - 1 - n_reg][d].  tokens >= 2 + n_reg.  A kept row has the bits
+ * vittf_gemm_kfeat_parts gives it when the register rows are taken out of `a`. */
+int vittf_gemm_kfeat_parts_reg(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                               int32_t tokens, int32_t n_reg, int32_t part_mask, void* q_out, void* k_out, void* v_out,
+                               int32_t dtype, void* stream);
 
 /* Residual linear + the LayerNorm that follows it:  x[rows][n] (fp32) += a[rows][k] . w[n][k]^T + bias;
  * h[rows][n] (h16) = LayerNorm(x; ln_g, ln_b, ln_eps).  Replaces attn.proj + residual + norm2 and mlp.fc2 + residual +

@@ -89,10 +89,11 @@ def get_dino_model(name):
 
 
 def get_dinov2_model(name):
-    """HIP engine for ``dinov2_<name>`` (vits14 / vitb14 / vitl14): the same loading as get_dino_model; the LayerScale gammas
-    of the checkpoint are folded into the weights (vt.fold_layer_scale)."""
-    if name == 'vitg14':
-        print('dinov2_vitg14 is not supported by the HIP engine: its FFN is SwiGLU and its width D = 1536 is beyond the '
+    """HIP engine for ``dinov2_<name>`` (vits14 / vitb14 / vitl14 and their register variants vits14_reg / vitb14_reg /
+    vitl14_reg): the same loading as get_dino_model; the LayerScale gammas of the checkpoint are folded into the weights
+    (vt.fold_layer_scale), the register tokens go to the engine as they are."""
+    if name in ('vitg14', 'vitg14_reg'):
+        print(f'dinov2_{name} is not supported by the HIP engine: its FFN is SwiGLU and its width D = 1536 is beyond the '
               "engine's 1024.  Use vits14, vitb14 or vitl14.")
         sys.exit(1)
     return _engine_model(name, 'dinov2')
@@ -262,12 +263,12 @@ def _agree_on_output_path(args, rank, world):
 def main(argv=None):
     from argparse import ArgumentParser
     dino_archs = ['vits16', 'vits8', 'vitb16', 'vitb8']
-    dino2_archs = ['vits14', 'vitb14', 'vitl14', 'vitg14']
+    dino2_archs = ['vits14', 'vitb14', 'vitl14', 'vitg14', 'vits14_reg', 'vitb14_reg', 'vitl14_reg', 'vitg14_reg']
     parser = ArgumentParser('Infer DINO features from saved volume')
     parser.add_argument('--data-path', type=str, required=True, help='volume file (.npy / .pt) to extract features from')
     parser.add_argument('--cache-path', type=str, default=None, help='where the feature file goes (default: next to the volume)')
     parser.add_argument('--dino-model', type=str, choices=dino_archs, default=None, help='DINO ViT variant')
-    parser.add_argument('--dino2-model', type=str, choices=dino2_archs, default=None, help='DINOv2 variant (patch 14; vitg14 is not supported: SwiGLU FFN, D = 1536)')
+    parser.add_argument('--dino2-model', type=str, choices=dino2_archs, default=None, help='DINOv2 variant (patch 14; _reg: with 4 register tokens; vitg14 is not supported: SwiGLU FFN, D = 1536)')
     parser.add_argument('--slice-along', type=str, choices=['x', 'y', 'z', 'all'], default='all',
                         help='Along which axis to slice volume, as it is fed slice-wise to DINO')
     parser.add_argument('--batch-size', type=int, default=1, help='a LOWER bound on the slices per engine call (the engine sizes its own calls: 256 x 4097 / tokens by '

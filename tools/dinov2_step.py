@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Time one feature-volume step of DINOv2 ViT-S/14 against DINO ViT-S/8 on the benchmark's workload (one GPU).
 
-    python tools/dinov2_step.py [--workload 512] [--steps 3] [--warmup 1]
+    python tools/dinov2_step.py [--workload 512] [--steps 3] [--warmup 1] [--archs A B ...] [--repeats R]
 
 Both models see the same volume at feature_output_size 64: 896 x 896 images at patch 14 and 512 x 512 at patch 8, both
 64 x 64 tokens (N = 4097), 1536 slices per step for the 512^3 volume.  Seeded synthetic weights (the timing does not depend
 on them).  Timed steps run without the profiler; one more step per model is run with vittf_profiler_* on, for the per-class
 milliseconds.  Prints ONE JSON line: slices/s of each model, their ratio, per-class ms per step, and the patch embedding's
 ms per 256 slices.
+
+--archs picks the models (default: vits14 vits8), e.g. ``--archs vits14 vits14_reg`` for the cost of the four register
+tokens (N = 4101 against 4097); the ratio on the line is first over second.  --repeats R runs the list R times in that
+order, so the models alternate: the line then carries every run's slices/s under ``runs`` (the spread of repeated runs of
+one model is the yardstick for a difference between two), and each model's entry is its last run.
 """
 import argparse
 import json
@@ -43,7 +48,8 @@ def run(arch, vol, fos, steps, warmup):
     finally:
         vt._lib.profiler_enable(False)
     ms = {k: round(v[0], 3) for k, v in prof.items() if v[1]}
-    res = {'arch': arch, 'image': list(im_sz), 'tokens': (im_sz[0] // model.patch_size) * (im_sz[1] // model.patch_size) + 1,
+    res = {'arch': arch, 'image': list(im_sz),
+           'tokens': (im_sz[0] // model.patch_size) * (im_sz[1] // model.patch_size) + 1 + model.num_register_tokens,
            'slices_per_step': slices, 'ms_per_step': round(sec * 1e3, 2), 'slices_per_s': round(slices / sec, 1),
            'class_ms_per_step': ms, 'patch_embed_kernel': vt._lib.kernel_name('patch_embed'),
            'patch_embed_ms_per_256_slices': round(prof['patch_embed'][0] * 256 / slices, 3),
@@ -59,16 +65,27 @@ def main():
     ap.add_argument('--fos', type=int, default=64)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--archs', nargs='+', default=['vits14', 'vits8'], help='models to time, in order (default: vits14 vits8)')
+    ap.add_argument('--repeats', type=int, default=1, help='run the list this many times, alternating the models')
     args = ap.parse_args()
+    if len(set(args.archs)) != len(args.archs) or len(args.archs) < 2:
+        ap.error('--archs takes two or more different models')
     import torch
     import bench
     import vit_tf_amd as vt
     torch.cuda.set_device(0)
     vol, _, desc = bench.make_workload(args.workload, vt)
-    res = {name: run(name, vol, args.fos, args.steps, args.warmup) for name in ('vits14', 'vits8')}
+    res, runs = {}, {name: [] for name in args.archs}
+    for _ in range(max(1, args.repeats)):
+        for name in args.archs:
+            res[name] = run(name, vol, args.fos, args.steps, args.warmup)
+            runs[name].append(res[name]['slices_per_s'])
+    a, b = args.archs[0], args.archs[1]
     line = {'tool': 'dinov2_step', 'workload': args.workload, 'fos': args.fos, 'steps': args.steps,
-            'device': torch.cuda.get_device_name(0), 'vits14': res['vits14'], 'vits8': res['vits8'],
-            'vits14_over_vits8_slices_per_s': round(res['vits14']['slices_per_s'] / res['vits8']['slices_per_s'], 4)}
+            'device': torch.cuda.get_device_name(0), **{name: res[name] for name in args.archs},
+            f'{a}_over_{b}_slices_per_s': round(res[a]['slices_per_s'] / res[b]['slices_per_s'], 4)}
+    if args.repeats > 1:
+        line['runs'] = runs
     print(json.dumps(line))
 
 

@@ -64,13 +64,18 @@ SIGNATURES = {
                                        _vp, _vp, _sz, _vp]),
     'vittf_vit_qkv_features': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
                                          _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_vit_qkv_features_reg': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
+                                             _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_profiler_enable': (C.c_int, [_i32]),
     'vittf_profiler_collect': (C.c_int, [_P(C.c_double), _P(_i64)]),
     'vittf_profiler_kernel_name': (C.c_char_p, [_i32]),
     'vittf_patch_embed': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _vp, _vp]),
+    'vittf_patch_embed_reg': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _vp, _i32, _vp,
+                                        _vp]),
     'vittf_layernorm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, _vp]),
     'vittf_gemm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     'vittf_gemm_kfeat_parts': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
+    'vittf_gemm_kfeat_parts_reg': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     'vittf_gemm_residual_ln': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp]),
     'vittf_block_tail_workspace_bytes': (_sz, []),
     'vittf_block_tail': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _vp]),
@@ -138,6 +143,7 @@ def load():
 KERNEL_CLASSES = ('patch_embed', 'layernorm', 'gemm', 'attention', 'mlp', 'gemm_qkv', 'gemm_proj', 'gemm_fc1', 'gemm_fc2',
                   'similarity')
 ABI_VERSION = 6
+MAX_REGISTER_TOKENS = 8   # VITTF_MAX_REGISTER_TOKENS
 QUERY_MAX_A = 64          # VITTF_QUERY_MAX_A: annotations of a vittf_similarity_query call
 
 

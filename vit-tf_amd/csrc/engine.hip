@@ -5,7 +5,7 @@
 // then only LayerNorm1 + the requested thirds (q, k, v) of the last block's qkv projection, in one launch -- the rest
 // of block L and the final norm never influence the hooked tensor, so they are not executed.
 //
-// Workspace layout for `batch` slices of N tokens (rows = batch * N, padded to the GEMM tile):
+// Workspace layout for `batch` slices of N tokens (N = f0*f1 + 1 + register tokens; rows = batch * N, padded to the GEMM tile):
 //   X    fp32 [rows][D]      residual stream
 //   H    h16  [rows][D]      LayerNorm output / attention output (MFMA operand)
 //   QKV  h16  [rows][3D]     attention input; QKV|O is re-used as the [rows][4D] MLP hidden buffer
@@ -103,11 +103,15 @@ extern "C" size_t vittf_vit_workspace_bytes(const vittf_vit_config* cfg, int32_t
                    cfg->attention_fp8 ? vittf_attention_fp8_workspace_bytes(batch, tokens, cfg->heads) : 0).total;
 }
 
-extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
-                                      const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
-                                      uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes,
-                                      void* stream) {
+// n_reg register tokens (DINOv2 _reg models) sit behind CLS in every slice: rows 1 .. n_reg of the residual stream are
+// reg_rows ([n_reg][D] fp32, no position embedding), they take part in every block like any token, and they leave with CLS
+// in the K-feature epilogue.  n_reg = 0 is the plain layout.
+extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                          const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                          const float* reg_rows, int32_t n_reg, uint16_t* q_out, uint16_t* k_out,
+                                          uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
   if (!config_ok(cfg) || !w || !pos || !view || !ws || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
+  if (n_reg < 0 || n_reg > VITTF_MAX_REGISTER_TOKENS || (n_reg > 0 && !reg_rows)) return VITTF_ERR_INVALID_ARG;
   if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
   if (((part_mask & 1) && !q_out) || ((part_mask & 2) && !k_out) || ((part_mask & 4) && !v_out)) return VITTF_ERR_INVALID_ARG;
   if (!w->qkv_w || !w->qkv_b || !w->proj_w || !w->proj_b || !w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b ||
@@ -115,7 +119,7 @@ extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_v
     return VITTF_ERR_INVALID_ARG;
   const int d = cfg->embed_dim, p = cfg->patch, L = cfg->depth, dt = cfg->dtype;
   if (view->out_rows % p || view->out_cols % p) return VITTF_ERR_INVALID_ARG;
-  const int tokens = (view->out_rows / p) * (view->out_cols / p) + 1;
+  const int tokens = (view->out_rows / p) * (view->out_cols / p) + 1 + n_reg;
   const int64_t rows = (int64_t)batch * tokens;
   // the GEMM kernels index a call's widest buffer -- [rows][4 D] 16-bit hidden values, [rows][3 D] on the block-tail path -- with
   // 32-bit element offsets: a batch beyond that is refused, not computed wrong (ViT-B/8 at N = 4097: 341 slices)
@@ -131,7 +135,7 @@ extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_v
   void* G = QKV;  // [rows][4D] hidden, aliases QKV|O (both dead while the MLP runs)
 
   int rc;
-  { ProfScope ps(VITTF_KERNEL_PATCH_EMBED, stream); rc = vittf_patch_embed(cfg, w, pos, view, slice0, batch, X, stream); }
+  { ProfScope ps(VITTF_KERNEL_PATCH_EMBED, stream); rc = vittf_patch_embed_reg(cfg, w, pos, view, slice0, batch, reg_rows, n_reg, X, stream); }
   if (rc) return rc;
   const size_t esz = 2;
   // Every LayerNorm but the first rides on the kernel in front of it (D = 384: the block tail; D = 768: the epilogue of the
@@ -157,8 +161,8 @@ extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_v
     if (l == L - 1) {
       // hooked tensor, the requested thirds only: rows [part*D, (part+1)*D) of qkv.weight / qkv.bias  (infer.py:189-209)
       ProfScope ps(VITTF_KERNEL_GEMM, stream);   // the K-feature projection: one launch for every requested third
-      return vittf_gemm_kfeat_parts(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, rows, d, d, tokens, part_mask, q_out, k_out, v_out,
-                                    dt, stream);
+      return vittf_gemm_kfeat_parts_reg(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, rows, d, d, tokens, n_reg, part_mask, q_out, k_out,
+                                        v_out, dt, stream);
     }
     { ProfScope ps(VITTF_KERNEL_GEMM_QKV, stream);
       if (fp8_rows)
@@ -218,6 +222,14 @@ extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_v
     if (rc) return rc;
   }
   return VITTF_OK;
+}
+
+extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                      const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                      uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes,
+                                      void* stream) {
+  return vittf_vit_qkv_features_reg(cfg, w, pos, view, slice0, batch, part_mask, nullptr, 0, q_out, k_out, v_out, ws, ws_bytes,
+                                    stream);
 }
 
 // one third: the same forward with a one-bit mask (the bytes of the single-third projection)

@@ -67,11 +67,11 @@ __global__ __launch_bounds__(384) void patch_embed_kernel(vittf_slice_view view,
                                                           const float* __restrict__ bias,
                                                           const float* __restrict__ cls_pos0,
                                                           const float* __restrict__ patch_pos, float* __restrict__ tokens_out,
-                                                          int d, int f0, int f1) {
+                                                          int d, int f0, int f1, int nreg, const float* __restrict__ reg_rows) {
   constexpr int PP = P * P;
   __shared__ __attribute__((aligned(16))) float px[TP][PP + 4];   // row stride 16-byte aligned: phase 2 reads float4 along k
   const int npatch = f0 * f1;
-  const int tokens = npatch + 1;
+  const int tokens = npatch + 1 + nreg;      // row 0 CLS, rows 1 .. nreg the register tokens (DINOv2 _reg models), then the patches
   const int b = blockIdx.y;
   const int p0 = blockIdx.x * TP;
   const float lo = view.minmax[0], hi = view.minmax[1];
@@ -100,6 +100,7 @@ __global__ __launch_bounds__(384) void patch_embed_kernel(vittf_slice_view view,
   __syncthreads();
 
   float* out_b = tokens_out + (int64_t)b * tokens * d;
+  float* out_p = out_b + (int64_t)nreg * d;      // patch p goes to row 1 + nreg + p
   for (int dd = threadIdx.x; dd < d; dd += blockDim.x) {
     float acc[TP];
 #pragma unroll
@@ -122,10 +123,12 @@ __global__ __launch_bounds__(384) void patch_embed_kernel(vittf_slice_view view,
 #pragma unroll
     for (int i = 0; i < TP; ++i) {
       const int p = p0 + i;
-      if (p < npatch) out_b[(int64_t)(1 + p) * d + dd] = acc[i] + bv + patch_pos[(int64_t)p * d + dd];
+      if (p < npatch) out_p[(int64_t)(1 + p) * d + dd] = acc[i] + bv + patch_pos[(int64_t)p * d + dd];
     }
-    if (blockIdx.x == 0) out_b[dd] = cls_pos0[dd];
   }
+  // rows 0 .. nreg of the slice, contiguous: cls_token + pos[0], then the register rows as they are (no position embedding)
+  if (blockIdx.x == 0)
+    for (int e = threadIdx.x; e < (1 + nreg) * d; e += blockDim.x) out_b[e] = e < d ? cls_pos0[e] : reg_rows[e - d];
 }
 
 // ---------------------------------------------------------------- patch embed on the matrix cores (D = 384, P = 8)
@@ -140,13 +143,15 @@ __global__ __launch_bounds__(384) void patch_embed_kernel(vittf_slice_view view,
 //     exactly the B operand's k = 16 s + 8 h + e -- with sample_kernel's nearest-resize arithmetic, so no pixel goes through LDS;
 //   * two passes of 6 output tiles (96 accumulator registers); epilogue from the accumulator layout: lane owns row j, columns
 //     32 ot + 8 g + 4 h + {0 .. 3}: + bias + position embedding as 16-byte loads, 16-byte stores (48 of each per 32 rows: far
-//     below this kernel's budget); the CLS row of a slice takes cls_token + pos[0].
+//     below this kernel's budget); the CLS row of a slice takes cls_token + pos[0], rows 1 .. nreg
+//     the register rows as they are.
 constexpr int PEM_D = 384, PEM_K = 64, PEM_FRAGS = (PEM_D / 32) * (PEM_K / 16) * 2;
 __global__ __launch_bounds__(512, 1) void patch_embed_mfma_kernel(vittf_slice_view view, int slice0, int batch,
                                                                   const float* __restrict__ w_t, const float* __restrict__ bias,
                                                                   const float* __restrict__ cls_pos0,
                                                                   const float* __restrict__ patch_pos,
-                                                                  float* __restrict__ tokens_out, int f0, int f1) {
+                                                                  float* __restrict__ tokens_out, int f0, int f1, int nreg,
+                                                                  const float* __restrict__ reg_rows) {
   __shared__ __attribute__((aligned(16))) unsigned short wlds[PEM_FRAGS * 512];      // 96 KB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(512, 1) void patch_embed_mfma_kernel(vittf_slice_vi
     }
   }
   __syncthreads();
-  const int npatch = f0 * f1, tokens = npatch + 1;
+  const int npatch = f0 * f1, tokens = npatch + 1 + nreg;
   const int64_t rows = (int64_t)batch * tokens;
   const float lo_v = view.minmax[0], range = view.minmax[1] - view.minmax[0];
   const float sr = (float)view.in_rows / (float)view.out_rows;
@@ -176,8 +181,10 @@ __global__ __launch_bounds__(512, 1) void patch_embed_mfma_kernel(vittf_slice_vi
     const bool valid = r < rows;
     const int b = valid ? (int)(r / tokens) : 0;
     const int t = valid ? (int)(r - (int64_t)b * tokens) : 0;
-    const bool patch = valid && t > 0;
-    const int p = patch ? t - 1 : 0;
+    const bool patch = valid && t > nreg;
+    const int p = patch ? t - 1 - nreg : 0;
+    // rows 0 .. nreg of a slice are copies: cls_token + pos[0], then the register rows (t = 0 whenever nreg = 0)
+    const float* crow = t == 0 ? cls_pos0 : reg_rows + (int64_t)(t - 1) * PEM_D;
     const int py = p / f1, pxx = p - py * f1;
     const float* slice = view.vol + (int64_t)(slice0 + b) * view.stride_slice;
     // the B operands: k step s = patch row 2 s + h, 8 columns
@@ -234,7 +241,7 @@ __global__ __launch_bounds__(512, 1) void patch_embed_mfma_kernel(vittf_slice_vi
               o.x = acc[j][4 * g + 0] + bv.x + pv.x; o.y = acc[j][4 * g + 1] + bv.y + pv.y;
               o.z = acc[j][4 * g + 2] + bv.z + pv.z; o.w = acc[j][4 * g + 3] + bv.w + pv.w;
             } else {
-              o = *reinterpret_cast<const float4*>(cls_pos0 + c);
+              o = *reinterpret_cast<const float4*>(crow + c);
             }
             *reinterpret_cast<float4*>(orow + c) = o;
           }
@@ -259,7 +266,8 @@ __global__ __launch_bounds__(512, 1) void patch_embed14_mfma_kernel(vittf_slice_
                                                                     const float* __restrict__ bias,
                                                                     const float* __restrict__ cls_pos0,
                                                                     const float* __restrict__ patch_pos,
-                                                                    float* __restrict__ tokens_out, int f0, int f1) {
+                                                                    float* __restrict__ tokens_out, int f0, int f1, int nreg,
+                                                                    const float* __restrict__ reg_rows) {
   __shared__ __attribute__((aligned(16))) unsigned short wlds[PE14_FRAGS * 512];      // 112 KB
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
@@ -281,7 +289,7 @@ __global__ __launch_bounds__(512, 1) void patch_embed14_mfma_kernel(vittf_slice_
     }
   }
   __syncthreads();
-  const int npatch = f0 * f1, tokens = npatch + 1;
+  const int npatch = f0 * f1, tokens = npatch + 1 + nreg;
   const int64_t rows = (int64_t)batch * tokens;
   const float lo_v = view.minmax[0], range = view.minmax[1] - view.minmax[0];
   const float sr = (float)view.in_rows / (float)view.out_rows;
@@ -292,8 +300,10 @@ __global__ __launch_bounds__(512, 1) void patch_embed14_mfma_kernel(vittf_slice_
     const bool valid = r < rows;
     const int b = valid ? (int)(r / tokens) : 0;
     const int t = valid ? (int)(r - (int64_t)b * tokens) : 0;
-    const bool patch = valid && t > 0;
-    const int p = patch ? t - 1 : 0;
+    const bool patch = valid && t > nreg;
+    const int p = patch ? t - 1 - nreg : 0;
+    // rows 0 .. nreg of a slice are copies: cls_token + pos[0], then the register rows (t = 0 whenever nreg = 0)
+    const float* crow = t == 0 ? cls_pos0 : reg_rows + (int64_t)(t - 1) * PEM_D;
     const int py = p / f1, pxx = p - py * f1;
     const float* slice = view.vol + (int64_t)(slice0 + b) * view.stride_slice;
     // source columns of the 8 image columns of this lane's half (nearest resize; half 1's last two are the padded taps)
@@ -352,7 +362,7 @@ __global__ __launch_bounds__(512, 1) void patch_embed14_mfma_kernel(vittf_slice_
             o.x = acc[j][4 * g + 0] + bv.x + pv.x; o.y = acc[j][4 * g + 1] + bv.y + pv.y;
             o.z = acc[j][4 * g + 2] + bv.z + pv.z; o.w = acc[j][4 * g + 3] + bv.w + pv.w;
           } else {
-            o = *reinterpret_cast<const float4*>(cls_pos0 + c);
+            o = *reinterpret_cast<const float4*>(crow + c);
           }
           *reinterpret_cast<float4*>(orow + c) = o;
         }
@@ -377,10 +387,11 @@ extern "C" int vittf_volume_minmax(const float* vol, int64_t n, float* out_minma
   return vittf_check_launch();
 }
 
-extern "C" int vittf_patch_embed(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
-                                 const vittf_slice_view* view, int32_t slice0, int32_t batch, float* tokens_out,
-                                 void* stream) {
+extern "C" int vittf_patch_embed_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                     const vittf_slice_view* view, int32_t slice0, int32_t batch, const float* reg_rows,
+                                     int32_t n_reg, float* tokens_out, void* stream) {
   if (!cfg || !w || !pos || !view || !tokens_out || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
+  if (n_reg < 0 || n_reg > VITTF_MAX_REGISTER_TOKENS || (n_reg > 0 && !reg_rows)) return VITTF_ERR_INVALID_ARG;
   if (!w->pe_w_t || !w->pe_b || !pos->cls_plus_pos0 || !pos->patch_pos || !view->vol || !view->minmax)
     return VITTF_ERR_INVALID_ARG;
   const int p = cfg->patch;
@@ -390,43 +401,51 @@ extern "C" int vittf_patch_embed(const vittf_vit_config* cfg, const vittf_vit_we
   const int f0 = view->out_rows / p, f1 = view->out_cols / p;
   const int nblk = (f0 * f1 + TP - 1) / TP;
   hipStream_t st = (hipStream_t)stream;
-  const bool aligned = (((uintptr_t)w->pe_b | (uintptr_t)pos->cls_plus_pos0 | (uintptr_t)pos->patch_pos | (uintptr_t)tokens_out) & 15) == 0;
+  // (the matrix-core kernels move whole rows as 16-byte pieces: a row is D * 4 bytes, so the rows behind the registers stay aligned)
+  const bool aligned = (((uintptr_t)w->pe_b | (uintptr_t)pos->cls_plus_pos0 | (uintptr_t)pos->patch_pos | (uintptr_t)tokens_out |
+                         (n_reg > 0 ? (uintptr_t)reg_rows : 0)) & 15) == 0;
   if (cfg->embed_dim == PEM_D && p == 8 && aligned) {
     // ViT-S/8: the conv on the matrix cores with fp16 head + tail operands (see patch_embed_mfma_kernel)
     const int cus = vittf_current_cus();
     if (cus <= 0) return VITTF_ERR_NO_DEVICE;
-    const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1) + 255) / 256;
+    const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1 + n_reg) + 255) / 256;
     vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_mfma_kernel");
     hipLaunchKernelGGL(patch_embed_mfma_kernel, dim3((unsigned)(ntile < cus ? ntile : cus)), dim3(512), 0, st, *view, slice0, batch,
-                       w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1);
+                       w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1, n_reg, reg_rows);
     return vittf_check_launch();
   }
   if (cfg->embed_dim == PEM_D && p == PE14_P && aligned) {
     // DINOv2 ViT-S/14: the same on the matrix cores, one workgroup per group of 4 output tiles (patch_embed14_mfma_kernel)
     const int cus = vittf_current_cus();
     if (cus <= 0) return VITTF_ERR_NO_DEVICE;
-    const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1) + 255) / 256;
+    const int64_t ntile = ((int64_t)batch * (f0 * f1 + 1 + n_reg) + 255) / 256;
     const int per_group = cus / PE14_GROUPS > 0 ? cus / PE14_GROUPS : 1;
     const int wgs = (int)(ntile < per_group ? ntile : per_group);
     vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed14_mfma_kernel");
     hipLaunchKernelGGL(patch_embed14_mfma_kernel, dim3((unsigned)(PE14_GROUPS * wgs)), dim3(512), 0, st, *view, slice0, batch,
-                       w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1);
+                       w->pe_w_t, w->pe_b, pos->cls_plus_pos0, pos->patch_pos, tokens_out, f0, f1, n_reg, reg_rows);
     return vittf_check_launch();
   }
   const int threads = cfg->embed_dim % 384 == 0 ? 384 : 256;   // one feature per thread in a single pass for D = 384 / 768
   if (p == 8) {
     vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<8>");
     hipLaunchKernelGGL((patch_embed_kernel<8>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
-                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
+                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1, n_reg, reg_rows);
   } else if (p == 14) {
     // 196 taps = 49 steps of the kernel's 4-k loop
     vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<14>");
     hipLaunchKernelGGL((patch_embed_kernel<14>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
-                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
+                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1, n_reg, reg_rows);
   } else {
     vittf_note_kernel(VITTF_KERNEL_PATCH_EMBED, "patch_embed_kernel<16>");
     hipLaunchKernelGGL((patch_embed_kernel<16>), dim3(nblk, batch), dim3(threads), 0, st, *view, slice0, w->pe_w_t, w->pe_b,
-                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1);
+                       pos->cls_plus_pos0, pos->patch_pos, tokens_out, cfg->embed_dim, f0, f1, n_reg, reg_rows);
   }
   return vittf_check_launch();
+}
+
+extern "C" int vittf_patch_embed(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                 const vittf_slice_view* view, int32_t slice0, int32_t batch, float* tokens_out,
+                                 void* stream) {
+  return vittf_patch_embed_reg(cfg, w, pos, view, slice0, batch, nullptr, 0, tokens_out, stream);
 }

@@ -49,6 +49,7 @@ struct KfeatParts {
   unsigned short* out[3];   // by third (q, k, v)
   int part[3];              // slot -> third
   int d;
+  int drop;                 // leading rows of a slice that are dropped: CLS + the register tokens
 };
 
 template <int DT, int EPI>
@@ -210,8 +211,10 @@ __global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __re
       if constexpr (EPI == VITTF_EPI_KFEAT || EPI == EPI_KFEAT_PARTS) {
         const int64_t b = m / tokens;
         const int tok = (int)(m - b * tokens);
-        if (tok == 0) continue;  // CLS row dropped (infer.py:202 k[:, 1:])
-        orow = b * (tokens - 1) + tok - 1;
+        // CLS row dropped (infer.py:202 k[:, 1:]); the several-thirds form also drops the register rows behind it
+        const int drop = EPI == EPI_KFEAT_PARTS ? kp.drop : 1;
+        if (tok < drop) continue;
+        orow = b * (tokens - drop) + tok - drop;
       }
       const uint4 v = *reinterpret_cast<const uint4*>(smem + rl * CS + (tid & 15) * 16);
       if constexpr (EPI == EPI_KFEAT_PARTS)
@@ -259,8 +262,8 @@ int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, in
                   int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st);   // gemm_pp.hip; 1 = not covered
 
 int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
-                              int32_t tokens, int32_t part_mask, void* const outs[3], int32_t dtype, hipStream_t st,
-                              int32_t* taken);   // gemm_pp.hip
+                              int32_t tokens, int32_t n_reg, int32_t part_mask, void* const outs[3], int32_t dtype,
+                              hipStream_t st, int32_t* taken);   // gemm_pp.hip
 
 // K >= 768 with N % 256 == 0 (the ViT-B linears) run on the persistent 256 x 256 kernel of gemm_pp.hip.  Residual linears with
 // 768 output columns take it from K = 3072 on (fc2: the LayerNorm behind it then runs as its own launch instead of in the
@@ -292,12 +295,14 @@ extern "C" int vittf_gemm(const void* a, const void* w, const float* bias, void*
 // The thirds of attn.qkv selected by part_mask (bit 0 q, 1 k, 2 v) in one launch per kernel, each with the K-feature epilogue
 // into its own output.  Every third runs on the kernel its own vittf_gemm(EPI_KFEAT) call would take -- the persistent
 // 256 x 256 kernel where it covers the shape, alignment and output size, else the 128 x 128 tiles --, so its bits are that
-// call's.
-extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
-                                      int32_t tokens, int32_t part_mask, void* q_out, void* k_out, void* v_out, int32_t dtype,
-                                      void* stream) {
+// call's.  n_reg register tokens behind CLS (DINOv2 _reg models) are dropped with it: rows tok <= n_reg of a slice go, the
+// others move up by 1 + n_reg; the arithmetic of a kept row does not depend on n_reg.
+extern "C" int vittf_gemm_kfeat_parts_reg(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                                          int32_t tokens, int32_t n_reg, int32_t part_mask, void* q_out, void* k_out,
+                                          void* v_out, int32_t dtype, void* stream) {
   void* const outs[3] = {q_out, k_out, v_out};
-  if (!a || !w || !bias || rows <= 0 || d <= 0 || k <= 0 || tokens < 2) return VITTF_ERR_INVALID_ARG;
+  if (!a || !w || !bias || rows <= 0 || d <= 0 || k <= 0) return VITTF_ERR_INVALID_ARG;
+  if (n_reg < 0 || n_reg > VITTF_MAX_REGISTER_TOKENS || tokens < 2 + n_reg) return VITTF_ERR_INVALID_ARG;
   if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
   for (int p = 0; p < 3; ++p)
     if (((part_mask >> p) & 1) && !outs[p]) return VITTF_ERR_INVALID_ARG;
@@ -306,7 +311,7 @@ extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float*
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
   int32_t taken = 0;
-  const int rc = vittf_gemm_pp_kfeat_parts(a, w, bias, rows, d, k, tokens, part_mask, outs, dtype, st, &taken);
+  const int rc = vittf_gemm_pp_kfeat_parts(a, w, bias, rows, d, k, tokens, n_reg, part_mask, outs, dtype, st, &taken);
   if (rc != VITTF_OK) return rc;
   const int rest = part_mask & ~taken;
   if (!rest) return VITTF_OK;
@@ -317,11 +322,18 @@ extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float*
     if ((rest >> p) & 1) kp.part[slots++] = p;
   }
   kp.d = d;
+  kp.drop = 1 + n_reg;
   const int part_tiles = slots * (d / BN);
   vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_kernel");   // (the projection is the engine's last launch: its class name tells which ran)
   if (dtype == VITTF_BF16)
     return launch_gemm<VITTF_BF16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
   return launch_gemm<VITTF_FP16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
+}
+
+extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
+                                      int32_t tokens, int32_t part_mask, void* q_out, void* k_out, void* v_out, int32_t dtype,
+                                      void* stream) {
+  return vittf_gemm_kfeat_parts_reg(a, w, bias, rows, d, k, tokens, 0, part_mask, q_out, k_out, v_out, dtype, stream);
 }
 
 // x += a . w^T + bias (fp32 residual stream, n = 384), then h = LayerNorm(x; g, b) as the 16-bit operand of the next

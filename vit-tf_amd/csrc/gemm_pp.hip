@@ -78,7 +78,7 @@ __device__ __forceinline__ int pp_scale_exp(float amax) {
 // Several thirds of attn.qkv in one launch with the K-feature epilogue (entry point vittf_gemm_pp_kfeat_parts below; internal
 // epilogue id): W / bias are the whole projection, the grid covers the column tiles of the requested thirds only (slot s =
 // third part[s]), and each third leaves through a descriptor of its own over its own output (64-bit base, `bytes` long).
-// Dropped rows (CLS, rows past the end) are predicated off, not sent to an out-of-range offset; the tile's stores are then
+// Dropped rows (CLS and the register rows behind it, rows past the end) are predicated off, not sent to an out-of-range offset; the tile's stores are then
 // fewer than the counted waits of the next tile's first stages assume, so this epilogue ends on a full vmcnt(0).
 constexpr int PP_EPI_KFEAT_PARTS = 101;
 struct PpParts {
@@ -86,6 +86,7 @@ struct PpParts {
   int part[3];              // slot -> third
   int d;
   unsigned bytes;           // of each output
+  int drop;                 // leading rows of a slice that are dropped: CLS + the register tokens
 };
 
 struct Frags { s16x8_t a[4][2], w[2][2]; };      // [32-row block][k16 step]
@@ -397,8 +398,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
             const int64_t m = row0 + rl;
             const int64_t b = m / tokens;
             const int tok = (int)(m - b * tokens);
-            const int64_t orow = b * (tokens - 1) + tok - 1;
-            if (m < rows && tok != 0)        // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
+            const int64_t orow = b * (tokens - kp.drop) + tok - kp.drop;
+            if (m < rows && tok >= kp.drop)  // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
               __builtin_amdgcn_raw_buffer_store_b128(pk, rp, (int)(unsigned)((orow * kp.d + (n0 - third * kp.d) + 4 * ch) * 2),
                                                      0, PP_STORE_AUX);
           } else if constexpr (EPI == VITTF_EPI_KFEAT) {
@@ -498,13 +499,13 @@ int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, in
 // (same shape, alignment and output-size rules as vittf_gemm_pp + launch_pp; on [3 d][k] weights, a third's are 16-byte
 // aligned when the whole are) in one launch.  *taken = the thirds launched; the others are the caller's.
 int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
-                              int32_t tokens, int32_t part_mask, void* const outs[3], int32_t dtype, hipStream_t st,
-                              int32_t* taken) {
+                              int32_t tokens, int32_t n_reg, int32_t part_mask, void* const outs[3], int32_t dtype,
+                              hipStream_t st, int32_t* taken) {
   *taken = 0;
   if (k < 768 || k % (2 * PBK) != 0 || d % PBN != 0) return VITTF_OK;
   if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)d * 4 * 64 > 0x7fffffff) return VITTF_OK;
   if ((((uintptr_t)a | (uintptr_t)w) & 15) != 0) return VITTF_OK;
-  const int64_t ob = (rows - rows / tokens) * (int64_t)d * 2;
+  const int64_t ob = (rows - rows / tokens * (1 + n_reg)) * (int64_t)d * 2;     // (whole slices: the engine's case)
   if (ob > 0xfffffff0ll) return VITTF_OK;
   PpParts kp{};
   int slots = 0, mask = 0;
@@ -515,6 +516,7 @@ int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, i
   if (!mask) return VITTF_OK;
   kp.d = d;
   kp.bytes = (unsigned)ob;
+  kp.drop = 1 + n_reg;
   vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_pp_kernel");
   const int part_tiles = slots * (d / PBN);
   const int rc = dtype == VITTF_BF16

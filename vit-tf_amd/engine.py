@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from .weights import (arch_of, fold_layer_scale, fold_patch_embed, interpolate_pos_embed, pack_block_tail_weights,
-                      pack_row_images)
+                      pack_row_images, pos_embed_antialias_of, register_tokens_of)
 
 _TORCH_DT = {_lib.BF16: torch.bfloat16, _lib.FP16: torch.float16}
 
@@ -30,8 +30,10 @@ class HipViT:
     """Weights + workspace of one ViT on one GPU.
 
     state_dict: DINO-layout tensors (fp32, CPU or GPU; DINOv2's LayerScale gammas are folded in).  arch: DINO / DINOv2 name
-    ('vits8', 'vits14', ...) or
-    (embed_dim, depth, heads, patch).  dtype of the MFMA operands: 'fp16' (default: the reference's own GPU autocast
+    ('vits8', 'vits14', 'vits14_reg', ...) or
+    (embed_dim, depth, heads, patch).  A ``register_tokens`` key (1, R, D) makes it a register model (the DINOv2 ``_reg`` names
+    require it, a tuple arch follows the key): ``num_register_tokens`` = R rows behind CLS in every slice, kept on the device,
+    and the size-based antialiased position-embedding resize.  dtype of the MFMA operands: 'fp16' (default: the reference's own GPU autocast
     type, infer.py:309; meets the 1e-3 parity bound against the fp32 CPU path) or 'bf16' (opt-in: 8-bit mantissa,
     2.4e-3 .. 3.9e-3 against the CPU path).  attention: '16bit' (default) or 'fp8' -- BASELINE configs[3]'s fp8 MFMA
     attention path (e4m3 operands on the block-scaled matrix instruction; ~3e-2 on the features: opt-in).
@@ -55,6 +57,8 @@ class HipViT:
         self.cfg = _lib.VitConfig(dim, depth, heads, patch, self.dtype_id, 1e-6, 1 if attention == 'fp8' else 0, int(flags))
 
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items()}
+        self.num_register_tokens = register_tokens_of(arch, sd)
+        self._pos_antialias = pos_embed_antialias_of(arch, sd)
         # DINOv2 LayerScale (blocks.{i}.ls1 / ls2.gamma present, whatever the arch name): folded into attn.proj / mlp.fc2 in
         # fp32 before the one conversion to 16 bits -- the kernels see ordinary weights
         sd = fold_layer_scale(sd)
@@ -82,6 +86,8 @@ class HipViT:
             ptrs['tail_packed'] = self._t['tail_packed'].data_ptr()
             ptrs['qkv_packed'] = self._t['qkv_packed'].data_ptr()
         self.weights = _lib.VitWeights(**ptrs)
+        # [R][D] fp32 rows the embedding kernels copy behind CLS (no position embedding)
+        self._reg = sd['register_tokens'].reshape(-1, dim).to(dev).contiguous() if self.num_register_tokens else None
         self._cls = sd['cls_token'].reshape(1, 1, dim)
         self._pos = sd['pos_embed']
         self._pos_cache = {}
@@ -99,14 +105,14 @@ class HipViT:
         """Device position embedding for a rows x cols image: (PosEmbed struct, keep-alive tensors)."""
         key = (rows, cols)
         if key not in self._pos_cache:
-            pos = interpolate_pos_embed(self._pos, rows, cols, self.patch_size)[0]      # (1 + n, D)
+            pos = interpolate_pos_embed(self._pos, rows, cols, self.patch_size, antialias=self._pos_antialias)[0]      # (1 + n, D)
             cls0 = (self._cls[0, 0] + pos[0]).to(self.device).contiguous()
             patch = pos[1:].to(self.device).contiguous()
             self._pos_cache[key] = (_lib.PosEmbed(cls0.data_ptr(), patch.data_ptr()), cls0, patch)
         return self._pos_cache[key]
 
     def workspace(self, batch, tokens):
-        """The engine's workspace for `batch` slices of `tokens` tokens (grown on demand, kept)."""
+        """The engine's workspace for `batch` slices of `tokens` tokens (registers included; grown on demand, kept)."""
         need = self.lib.vittf_vit_workspace_bytes(C.byref(self.cfg), batch, tokens)
         if need == 0:
             raise _lib.VittfError('unsupported ViT configuration for the HIP engine')
@@ -115,36 +121,34 @@ class HipViT:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def tokens_for(self, view):
+        """Token rows of one slice of `view`: CLS + the register tokens + the f0 x f1 patches."""
+        p = self.patch_size
+        return (view.out_rows // p) * (view.out_cols // p) + 1 + self.num_register_tokens
+
     def k_features(self, view, slice0, batch, out, part=1):
         """Run slices [slice0, slice0+batch) of `view` (a _lib.SliceView) through the ViT and write the
         hooked qkv third (`part`: 0 q, 1 k, 2 v) of the patch tokens as fp16 into `out`
         (tensor of >= batch * f0*f1 * D halves)."""
-        p = self.patch_size
-        tokens = (view.out_rows // p) * (view.out_cols // p) + 1
-        pos, _, _ = self.pos_for(view.out_rows, view.out_cols)
-        ws = self.workspace(batch, tokens)
-        assert out.dtype == torch.float16 and out.is_contiguous() and out.numel() >= batch * (tokens - 1) * self.embed_dim
-        rc = self.lib.vittf_vit_k_features(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
-                                           slice0, batch, part, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr())
-        _lib.check(rc, 'vittf_vit_k_features')
+        self.qkv_features(view, slice0, batch, {int(part): out})
 
     def qkv_features(self, view, slice0, batch, outs):
         """One forward of slices [slice0, slice0+batch) for several thirds of the hooked qkv tensor: `outs` maps a part
         (0 q, 1 k, 2 v) to its output tensor, each written as k_features(part) writes it (same bits)."""
-        p = self.patch_size
-        tokens = (view.out_rows // p) * (view.out_cols // p) + 1
+        tokens = self.tokens_for(view)
+        npatch = tokens - 1 - self.num_register_tokens
         pos, _, _ = self.pos_for(view.out_rows, view.out_cols)
         ws = self.workspace(batch, tokens)
         ptrs = [None, None, None]
         for part, out in outs.items():
             assert out.dtype == torch.float16 and out.is_contiguous() and \
-                out.numel() >= batch * (tokens - 1) * self.embed_dim
+                out.numel() >= batch * npatch * self.embed_dim
             ptrs[int(part)] = _lib.ptr(out)
         mask = sum(1 << int(part) for part in outs)
-        rc = self.lib.vittf_vit_qkv_features(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
-                                             slice0, batch, mask, *ptrs, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, 'vittf_vit_qkv_features')
+        rc = self.lib.vittf_vit_qkv_features_reg(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
+                                                 slice0, batch, mask, _lib.ptr(self._reg), self.num_register_tokens, *ptrs,
+                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, 'vittf_vit_qkv_features_reg')
 
     def __call__(self, *_a, **_k):
         raise _lib.VittfError('HipViT is driven through compute_qkv / FeatureExtractor, not called on image tensors')

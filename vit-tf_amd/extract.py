@@ -37,18 +37,20 @@ class AtLeast(int):
     batch but never lowers it.  A plain int (bench.py --engine-batch, the tests) is taken literally."""
 
 
-def engine_batch_for(tokens, embed_dim, requested=None):
+def engine_batch_for(tokens, embed_dim, requested=None, n_reg=0):
     """Slices per engine call.  The default keeps the ROW count of a call at what 512 slices of N = 4097 are for D <= 384
     (2.1 M rows: 11 GB of workspace) and 256 slices for wider models (1.05 M rows: 11 GB at D = 768; the widest buffer, rows x
     4 D 16-bit values, stays below 2^32 elements), whatever the token count: base * 4097 / tokens, clamped to 1 .. base -- the
-    fos-128 preset (N = 16385) then runs 128 slices per call.  `requested`: a plain int (bench.py --engine-batch, tests) is
+    fos-128 preset (N = 16385) then runs 128 slices per call.  `tokens` includes a register model's `n_reg` register rows; the
+    default's row budget does not count them (N = 4101 stays at 512 / 256 slices: at 511 the benchmark's 1536 slices per axis
+    would end on a fourth call of 3 slices, one partial round of every kernel), every limit below does.  `requested`: a plain int (bench.py --engine-batch, tests) is
     taken literally, an `AtLeast` (infer.py --batch-size, compute_qkv's batch_size) only raises the default;
     VITTF_ENGINE_BATCH overrides both; results never depend on any of them."""
     env = __import__('os').environ.get('VITTF_ENGINE_BATCH')
     if env:
         return max(1, int(env))
     base = DEFAULT_ENGINE_BATCH if int(embed_dim) <= 384 else DEFAULT_ENGINE_BATCH_WIDE
-    default = max(1, min(base, base * 4097 // int(tokens)))
+    default = max(1, min(base, base * 4097 // max(1, int(tokens) - int(n_reg))))
     if int(embed_dim) > 768:
         # ViT-L (D = 1024): 256 slices of N = 4097 are 4.296e9 hidden values, over 2^32 -- cap the default and AtLeast
         default = min(default, wide_batch_limit(tokens, embed_dim))
@@ -64,7 +66,9 @@ def engine_batch_for(tokens, embed_dim, requested=None):
 def wide_batch_limit(tokens, embed_dim):
     """Most slices of `tokens` tokens one engine call of width `embed_dim` takes: its [rows][4 D] hidden buffer below 2^32
     elements (vittf_vit_qkv_features refuses more) and each K-feature output, batch x (tokens - 1) x D fp16 values, below
-    2^31 bytes (the persistent GEMM's dropped-row offset 0x80000000 must lie outside it).  N = 4097, D = 1024: 255 slices."""
+    2^31 bytes (the persistent GEMM's dropped-row offset 0x80000000 must lie outside it).  N = 4097, D = 1024: 255 slices.
+    `tokens` counts a register model's register rows (N = 4101 for ViT-L/14-reg: 255 slices too); its K-feature output has
+    fewer rows than tokens - 1, so the second bound only errs to the safe side."""
     tokens, d = int(tokens), int(embed_dim)
     by_hidden = (2 ** 32 - 1) // (tokens * 4 * d)
     by_kfeat = (2 ** 31 - 1) // (max(1, tokens - 1) * d * 2)
@@ -137,10 +141,17 @@ def _axis_geometry(shape, im_sizes, axis, patch):
     return sl, a, b, shape[sl], im_sizes[a] // patch, im_sizes[b] // patch
 
 
+def _slice_tokens(model, f0, f1):
+    """Token rows of one slice in the engine: CLS + the model's register tokens (DINOv2 _reg: 4) + the f0 x f1 patches.  Only the
+    batching sees them: every output, buffer and pooling call below is sized by the f0 * f1 patch tokens."""
+    return f0 * f1 + 1 + int(getattr(model, 'num_register_tokens', 0))
+
+
 def k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, part=1, out=None):
     """Token-major fp16 features of slices [s0, s1) of one axis: tensor [s1-s0, f0*f1, D] on the device."""
     _, _, _, _, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
-    engine_batch = engine_batch_for(f0 * f1 + 1, model.embed_dim, engine_batch)
+    engine_batch = engine_batch_for(_slice_tokens(model, f0, f1), model.embed_dim, engine_batch,
+                                    n_reg=int(getattr(model, 'num_register_tokens', 0)))
     n = s1 - s0
     per = f0 * f1 * model.embed_dim
     if out is None:
@@ -156,7 +167,8 @@ def qkv_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, parts=(0,
     """k_slices for several thirds of the hooked qkv tensor (`parts`: 0 q, 1 k, 2 v) from ONE engine forward per slice
     batch: a list of tensors [s1-s0, f0*f1, D], in the order of `parts`, each with the bits k_slices(part) gives."""
     _, _, _, _, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
-    engine_batch = engine_batch_for(f0 * f1 + 1, model.embed_dim, engine_batch)
+    engine_batch = engine_batch_for(_slice_tokens(model, f0, f1), model.embed_dim, engine_batch,
+                                    n_reg=int(getattr(model, 'num_register_tokens', 0)))
     n = s1 - s0
     per = f0 * f1 * model.embed_dim
     outs = [torch.empty((n, f0 * f1, model.embed_dim), dtype=torch.float16, device=model.device) for _ in parts]

@@ -13,6 +13,16 @@ restated from it like SURVEY.md 8a row a5 restates DINO's): ``img_size=518, patc
 scale-factor resize as DINO (stored grid 37 x 37).  Its block is ``x + ls1(attn(norm1(x)))``, ``x + ls2(mlp(norm2(x)))``
 with ``ls(y) = y * gamma`` (one gamma per channel): the checkpoint holds the DINO keys plus ``blocks.{i}.ls1.gamma``,
 ``blocks.{i}.ls2.gamma`` and ``mask_token`` (unused at inference).
+
+DINOv2 with registers (hub entries ``dinov2_vit{s,b,l}14_reg``, checkpoints ``dinov2_vit{s,b,l}14_reg4_pretrain.pth``; here
+``vits14_reg``, ``vitb14_reg``, ``vitl14_reg``): the plain entries with ``num_register_tokens=4``, ``interpolate_offset=0.0``
+and ``interpolate_antialias=True``.  The state dict gains ``register_tokens`` (1, 4, D); the token order is
+``[CLS, reg_0 .. reg_3, patch_0 ..]``: the position embedding is added to CLS and the patches, the registers are inserted
+afterwards and get none.  The stored grid is resized to the token grid by SIZE with antialiased bicubic interpolation
+(``F.interpolate(size=(r0, c0), mode='bicubic', antialias=True)``), not by the scale factor with the 0.1 offset.  The
+registers take part in the attention of every block and are dropped, with CLS, from the hooked q / k / v.  No ``_reg``
+checkpoint has been run through this code yet (none was available): the tests use synthetic weights in that layout.
+ViT-g/14 (with or without registers) is not built.
 """
 import math
 import os
@@ -30,8 +40,15 @@ ARCHS = {
     'vits14': (384, 12, 6, 14),
     'vitb14': (768, 12, 12, 14),
     'vitl14': (1024, 24, 16, 14),
+    # hub entries dinov2_<name>: the same with register tokens (REGISTER_TOKENS) and the size-based antialiased position resize
+    'vits14_reg': (384, 12, 6, 14),
+    'vitb14_reg': (768, 12, 12, 14),
+    'vitl14_reg': (1024, 24, 16, 14),
 }
-DINOV2_ARCHS = ('vits14', 'vitb14', 'vitl14')
+DINOV2_ARCHS = ('vits14', 'vitb14', 'vitl14', 'vits14_reg', 'vitb14_reg', 'vitl14_reg')
+# name: register tokens behind CLS (the state dict's ``register_tokens`` is (1, R, D)); every other name has none
+REGISTER_TOKENS = {'vits14_reg': 4, 'vitb14_reg': 4, 'vitl14_reg': 4}
+MAX_REGISTER_TOKENS = 8                 # what the engine's *_reg entry points take (VITTF_MAX_REGISTER_TOKENS)
 DINOV2_STORED_GRID = 37                 # 518 / 14
 # file names torch.hub would have cached for these entries
 HUB_FILES = {
@@ -42,6 +59,9 @@ HUB_FILES = {
     'vits14': 'dinov2_vits14_pretrain.pth',
     'vitb14': 'dinov2_vitb14_pretrain.pth',
     'vitl14': 'dinov2_vitl14_pretrain.pth',
+    'vits14_reg': 'dinov2_vits14_reg4_pretrain.pth',
+    'vitb14_reg': 'dinov2_vitb14_reg4_pretrain.pth',
+    'vitl14_reg': 'dinov2_vitl14_reg4_pretrain.pth',
 }
 IN_MEAN = (0.485, 0.456, 0.406)   # infer.py:39
 IN_STD = (0.229, 0.224, 0.225)    # infer.py:40
@@ -56,6 +76,33 @@ def arch_of(arch):
     return int(dim), int(depth), int(heads), int(patch)
 
 
+def register_tokens_of(arch, state_dict):
+    """Number of register tokens R of a model: for a name, REGISTER_TOKENS (0 for the plain names), checked against the state
+    dict's ``register_tokens`` key -- a checkpoint of the other family, or with another count, is refused; for an arch given
+    as a (D, depth, heads, patch) tuple, read off that key (no key: 0)."""
+    reg = state_dict.get('register_tokens')
+    have = 0
+    if reg is not None:
+        if reg.ndim != 3 or reg.shape[0] != 1 or reg.shape[2] != arch_of(arch)[0]:
+            raise ValueError(f'register_tokens has shape {tuple(reg.shape)}, expected (1, R, {arch_of(arch)[0]})')
+        have = int(reg.shape[1])
+    if isinstance(arch, str):
+        want = REGISTER_TOKENS.get(arch, 0)
+        if have != want:
+            raise ValueError(f'{arch} has {want} register tokens, the state dict has {have}'
+                             + (' (no register_tokens key)' if reg is None else ''))
+    if have > MAX_REGISTER_TOKENS:
+        raise ValueError(f'{have} register tokens: the engine takes at most {MAX_REGISTER_TOKENS}')
+    return have
+
+
+def pos_embed_antialias_of(arch, state_dict):
+    """Which position-embedding resize a model uses: True = the register models' size-based antialiased form
+    (interpolate_offset 0.0, interpolate_antialias True), False = the scale-factor form with the 0.1 offset (DINO, plain
+    DINOv2).  Upstream ties it to the hub entry; a tuple arch follows the presence of ``register_tokens``."""
+    return register_tokens_of(arch, state_dict) > 0
+
+
 # "massive activation" channels of the outlier variant below (trained ViTs carry a handful of residual-stream channels two
 # orders of magnitude above the rest; Gaussian unit-gain weights have none)
 OUTLIER_CHANNELS = (7, 100, 191, 250, 333, 380)
@@ -67,7 +114,9 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False,
     stored_grid: side of the stored position-embedding grid (default 28, 37 for the DINOv2 names).
     layer_scale: add the DINOv2 keys -- ``blocks.{i}.ls1.gamma`` / ``ls2.gamma``, log-uniform over [1e-5, 1] so that tiny
     gammas are exercised, and ``mask_token`` (default: True for the DINOv2 names only).  They are drawn from a generator of
-    their own, after every DINO tensor, so the DINO tensors of a seed do not depend on this flag.
+    their own, after every DINO tensor, so the DINO tensors of a seed do not depend on this flag.  The ``_reg`` names add
+    ``register_tokens`` (1, R, D), std 0.5, from a third generator after all of those: ``vits14_reg`` and ``vits14`` of one
+    seed agree on every shared key.
 
     outliers=True: the same weights with six massive channels planted -- x50 rows in two blocks' mlp.fc2 and one block's
     attn.proj (the residual stream then carries them to the end), x50 entries in several norm weights (16-bit LayerNorm
@@ -138,6 +187,10 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False,
         for i in range(depth):
             for ls in ('ls1', 'ls2'):
                 sd[f'blocks.{i}.{ls}.gamma'] = 10.0 ** (torch.rand(dim, generator=g2) * -5.0)
+    n_reg = REGISTER_TOKENS.get(arch, 0) if isinstance(arch, str) else 0
+    if n_reg:
+        g3 = torch.Generator().manual_seed(0x4e6157 + seed)
+        sd['register_tokens'] = torch.randn(1, n_reg, dim, generator=g3) * 0.5
     return sd
 
 
@@ -217,9 +270,11 @@ def fold_patch_embed(weight, bias):
     return w1.reshape(d, -1).t().contiguous().float(), b1.float()
 
 
-def interpolate_pos_embed(pos_embed, rows, cols, patch):
+def interpolate_pos_embed(pos_embed, rows, cols, patch, antialias=False):
     """Position embedding for a rows x cols pixel image, upstream form: bicubic,
     ``scale_factor=((r0 + 0.1) / sqrt(N), (c0 + 0.1) / sqrt(N))``; identity for the stored square grid.
+    antialias=True: the DINOv2 register models' form instead (interpolate_offset 0.0, interpolate_antialias True) --
+    ``size=(r0, c0)``, bicubic with antialias; the caller chooses by the model (pos_embed_antialias_of).
     Runs once per image size on the host (it depends on the weights only).  Returns (1, 1 + r0*c0, D)."""
     n_stored = pos_embed.shape[1] - 1
     r0, c0 = rows // patch, cols // patch
@@ -228,8 +283,11 @@ def interpolate_pos_embed(pos_embed, rows, cols, patch):
     dim = pos_embed.shape[-1]
     g = int(math.sqrt(n_stored))
     grid = pos_embed[:, 1:].reshape(1, g, g, dim).permute(0, 3, 1, 2)
-    grid = F.interpolate(grid.float(), scale_factor=((r0 + 0.1) / math.sqrt(n_stored), (c0 + 0.1) / math.sqrt(n_stored)),
-                         mode='bicubic')
+    if antialias:
+        grid = F.interpolate(grid.float(), size=(r0, c0), mode='bicubic', antialias=True)
+    else:
+        grid = F.interpolate(grid.float(), scale_factor=((r0 + 0.1) / math.sqrt(n_stored), (c0 + 0.1) / math.sqrt(n_stored)),
+                             mode='bicubic')
     if grid.shape[-2] != r0 or grid.shape[-1] != c0:
         raise ValueError(f'position-embedding grid {tuple(grid.shape[-2:])} != token grid {(r0, c0)}')
     grid = grid.permute(0, 2, 3, 1).reshape(1, -1, dim)
