@@ -57,7 +57,7 @@ typedef struct vittf_vit_config {
   int32_t heads;       /* D / 64 */
   int32_t patch;       /* P: 8, 14 (DINOv2) or 16 */
   int32_t dtype;       /* vittf_dtype of the MFMA operands */
-  float   ln_eps;      /* 1e-6 */
+  float   ln_eps;      /* 1e-6 (DINO, DINOv2), 1e-5 (DINOv3) */
   int32_t attention_fp8; /* 0: 16-bit attention (default).  1: the fp8 (e4m3) block-scaled MFMA attention path of BASELINE
                             configs[3] (vittf_attention_fp8): 3-mantissa-bit operands, ~3e-2 on the features -- opt-in */
   int32_t flags;       /* 0 = the measured path.  Bits select the slower alternatives the parity tests also run (ABI 6: they
@@ -161,6 +161,29 @@ int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weig
                                const float* reg_rows, int32_t n_reg, uint16_t* q_out, uint16_t* k_out, uint16_t* v_out,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* Rotary position embedding of DINOv3 for ONE image size: cos and sin of the 32 distinct angles of every patch token, fp32
+ * [patches = f0*f1][32], row-major over the patch grid.  Built on the host (vit-tf_amd/weights.py rope_table): with
+ * inv_freq[i] = 1 / 100^(i/16), cy = 2 (r + 0.5) / f0 - 1, cx = 2 (c + 0.5) / f1 - 1: angle[0:16] = 2 pi cy inv_freq,
+ * angle[16:32] = 2 pi cx inv_freq; columns j and j + 32 of a head of 64 share angle[j]. */
+typedef struct vittf_rope_table {
+  const float* cos;      /* [patches][32] */
+  const float* sin;      /* [patches][32] */
+  int32_t patches;       /* f0*f1 */
+} vittf_rope_table;
+
+/* vittf_vit_qkv_features_reg for a model with rotary position embedding (DINOv3 dinov3_vit{s,b,l}16): with a table, the q and
+ * k thirds of the patch tokens are rotated (vittf_rope_qk, prefix = 1 + n_reg) behind the qkv projection of every full block,
+ * on every qkv path and with VITTF_CFG_UNSCALED_Q; the hooked tensor of the last block is taken BEFORE the rotation, as the
+ * hook on blocks[-1].attn.qkv sees it.  The rotated q and k are rounded to h16 a second time (the projection's epilogue has
+ * rounded them once).  table->patches must be f0*f1.  cfg->attention_fp8 together with a table: VITTF_ERR_INVALID_ARG -- that
+ * path quantises q and k to fp8 inside the GEMM epilogue, before a rotation could happen.  Such a model has no additive
+ * position embedding: pass a zero pos->patch_pos and pos->cls_plus_pos0 = cls_token.  table == NULL is
+ * vittf_vit_qkv_features_reg, bit for bit.  [host] cfg, w, pos, view, table are host structs holding device pointers. */
+int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                const float* reg_rows, int32_t n_reg, const vittf_rope_table* table, uint16_t* q_out,
+                                uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Optional timing of the launches inside vittf_vit_k_features and vittf_similarity, by kernel class, with HIP events recorded on
  * the caller's stream (what bench.py's roofline leg reads).  Process-global, off by default, not thread-safe:
  * the one exception to "no global mutable state".  enable(mask) clears earlier records and starts recording the
@@ -171,7 +194,7 @@ typedef enum vittf_kernel_class {
   VITTF_KERNEL_PATCH_EMBED = 0, VITTF_KERNEL_LAYERNORM = 1,
   VITTF_KERNEL_GEMM = 2,        /* linears without a class of their own: the K-feature projection */
   VITTF_KERNEL_ATTENTION = 3, VITTF_KERNEL_MLP = 4,
-  VITTF_KERNEL_GEMM_QKV = 5,    /* attn.qkv (+ q pre-scale) */
+  VITTF_KERNEL_GEMM_QKV = 5,    /* attn.qkv (+ q pre-scale; + the DINOv3 rotation of q and k, vittf_rope_qk) */
   VITTF_KERNEL_GEMM_PROJ = 6,   /* attn.proj + residual (+ norm2) */
   VITTF_KERNEL_GEMM_FC1 = 7,    /* mlp.fc1 + GELU */
   VITTF_KERNEL_GEMM_FC2 = 8,    /* mlp.fc2 + residual (+ the next norm1) */
@@ -271,6 +294,16 @@ size_t vittf_block_tail_workspace_bytes(void);
 int vittf_block_tail(const void* attn_out, const void* w_packed, const float* proj_b, const float* ln2_g, const float* ln2_b,
                      const float* b1, const float* b2, float* x, int64_t rows, int32_t d, int32_t dtype, const float* ln_g,
                      const float* ln_b, float ln_eps, void* h_out, void* tile_counter, void* stream);
+
+/* DINOv3's rotary position embedding applied in place to the q and k thirds of qkv h16 [rows][3 * 64 * heads] (columns
+ * [q | k | v], heads of 64; 16-byte aligned): for every row with row % tokens >= prefix (a patch token; prefix = 1 + register
+ * tokens: CLS and the registers are left untouched), every head of q and of k and j < 32, with t = row % tokens - prefix:
+ *     x[j]'      = x[j] cos[t][j] - x[j + 32] sin[t][j]
+ *     x[j + 32]' = x[j + 32] cos[t][j] + x[j] sin[t][j]
+ * in fp32, rounded once to h16.  The v third is neither read nor written.  table->patches == tokens - prefix.  Works on q as
+ * VITTF_EPI_BIAS_QKV leaves it (a rotation commutes with the scale). */
+int vittf_rope_qk(void* qkv, int64_t rows, int32_t tokens, int32_t prefix, int32_t heads, const vittf_rope_table* table,
+                  int32_t dtype, void* stream);
 
 /* Multi-head self-attention over `batch` independent sequences of `tokens` rows.
  * qkv h16 [batch*tokens][3D] with columns [q | k | v], heads of 64 concatenated inside each third

@@ -77,7 +77,7 @@ def _engine_model(name, hub):
         print(f'Using seeded synthetic {name} weights (seed {seed}); features are NOT {hub.upper()} features.')
         sd = vt.synthetic_state_dict(name, seed)
     else:
-        print(f'No local checkpoint for {hub}_{name}: pass --weights PATH ({hub.upper()} state dict) or '
+        print(f'No local checkpoint for {name if name.startswith(hub) else hub + "_" + name}: pass --weights PATH ({hub.upper()} state dict) or '
               f'--synthetic-weights SEED. This build never downloads weights.')
         sys.exit(1)
     return vt.HipViT(sd, name, dtype=_MODEL_OPTS['dtype'], attention=_MODEL_OPTS['attention'])
@@ -99,11 +99,41 @@ def get_dinov2_model(name):
     return _engine_model(name, 'dinov2')
 
 
+DINOV3_UNSUPPORTED = {
+    'vits16plus': 'its MLP is a gated SwiGLU, which the HIP engine does not have',
+    'vith16plus': "its MLP is a gated SwiGLU and its width D = 1280 is not one of the engine's (384, 768, 1024)",
+    'vit7b16': "its width D = 4096 is beyond the engine's 1024 and its head dim is 128, not 64",
+}
+
+
+def get_dinov3_model(name):
+    """HIP engine for ``dinov3_<name>`` (vits16 / vitb16 / vitl16; `name` with or without the ``dinov3_`` prefix): the same
+    loading as get_dino_model, from --weights / $VITTF_WEIGHTS (Meta's .pth layout or the Hugging Face one, .safetensors
+    included) or --synthetic-weights; there is no hub-cache file name for these.  The rotary position embedding, the
+    LayerNorm eps 1e-5 and the zero key bias are the model's (vt.HipViT)."""
+    short = name[len('dinov3_'):] if name.startswith('dinov3_') else name
+    if short in DINOV3_UNSUPPORTED:
+        print(f'dinov3_{short} is not supported by the HIP engine: {DINOV3_UNSUPPORTED[short]}.  Use vits16, vitb16 or vitl16.')
+        sys.exit(1)
+    return _engine_model(f'dinov3_{short}', 'dinov3')
+
+
 def load_model(args):
     """(:239-264) -> (model name, constructor, patch size); exits with 1 on contradictory flags."""
+    dino3_model = getattr(args, 'dino3_model', None)
     if args.dino_model and args.dino2_model:
         print('Both --dino-model and --dino2-model were set. Please only set one of them.')
         sys.exit(1)
+    if dino3_model and (args.dino_model or args.dino2_model):
+        other = '--dino-model' if args.dino_model else '--dino2-model'
+        print(f'Both {other} and --dino3-model were set. Please only set one of them.')
+        sys.exit(1)
+    if dino3_model in DINOV3_UNSUPPORTED:
+        get_dinov3_model(dino3_model)           # prints the reason and exits with 1 before anything is loaded
+    if dino3_model:
+        # the prefix keeps the default cache file name apart from DINO's vits16 / vitb16
+        args.dino_model = args.model = f'dinov3_{dino3_model}'
+        return args.model, get_dinov3_model, 16
     if args.dino2_model:
         args.dino_model = args.model = args.dino2_model
         return args.dino2_model, get_dinov2_model, 14
@@ -269,6 +299,8 @@ def main(argv=None):
     parser.add_argument('--cache-path', type=str, default=None, help='where the feature file goes (default: next to the volume)')
     parser.add_argument('--dino-model', type=str, choices=dino_archs, default=None, help='DINO ViT variant')
     parser.add_argument('--dino2-model', type=str, choices=dino2_archs, default=None, help='DINOv2 variant (patch 14; _reg: with 4 register tokens; vitg14 is not supported: SwiGLU FFN, D = 1536)')
+    parser.add_argument('--dino3-model', type=str, choices=['vits16', 'vitb16', 'vitl16', *DINOV3_UNSUPPORTED], default=None,
+                        help='DINOv3 variant (patch 16, 4 register tokens, rotary position embedding; the plus and 7B models are not supported)')
     parser.add_argument('--slice-along', type=str, choices=['x', 'y', 'z', 'all'], default='all',
                         help='Along which axis to slice volume, as it is fed slice-wise to DINO')
     parser.add_argument('--batch-size', type=int, default=1, help='a LOWER bound on the slices per engine call (the engine sizes its own calls: 256 x 4097 / tokens by '
@@ -278,7 +310,7 @@ def main(argv=None):
     parser.add_argument('--cpu', action='store_true', help='Use CPU only (not available in the MI355X build)')
     parser.add_argument('--overwrite', action='store_true', help='replace an existing feature file')
     # additions of the MI355X build
-    parser.add_argument('--weights', type=str, default=None, help='Local DINO state dict (.pth)')
+    parser.add_argument('--weights', type=str, default=None, help='Local DINO / DINOv2 / DINOv3 state dict (.pth; DINOv3 also in the Hugging Face layout, .safetensors included)')
     parser.add_argument('--synthetic-weights', type=int, default=None, metavar='SEED', help='Use seeded synthetic weights')
     parser.add_argument('--engine-dtype', type=str, choices=['fp16', 'bf16'], default='fp16',
                         help='MFMA operand type (fp16 = the reference GPU autocast type, 1e-3 parity; bf16 opt-in)')

@@ -13,6 +13,8 @@ ms per 256 slices.
 tokens (N = 4101 against 4097); the ratio on the line is first over second.  --repeats R runs the list R times in that
 order, so the models alternate: the line then carries every run's slices/s under ``runs`` (the spread of repeated runs of
 one model is the yardstick for a difference between two), and each model's entry is its last run.
+``--archs dinov3_vits16 vits14_reg``: both run N = 4101 at D = 384, so the difference is DINOv3's rotation of q and k (inside
+the ``gemm_qkv`` class) plus the patch-16 against the patch-14 embedding.
 """
 import argparse
 import json

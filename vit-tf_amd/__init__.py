@@ -4,7 +4,7 @@ every compute entry point raises if the library or a gfx950 device is missing (n
 from . import _lib                                                  # noqa: F401
 from ._lib import VittfError                                        # noqa: F401
 from .weights import (ARCHS, synthetic_state_dict, load_state_dict_file, find_local_checkpoint,   # noqa: F401
-                      fold_patch_embed, fold_layer_scale, interpolate_pos_embed)
+                      fold_patch_embed, fold_layer_scale, interpolate_pos_embed, rope_table, dinov3_from_hf)
 from .engine import HipViT                                          # noqa: F401
 from .extract import (sizing, feature_volume, pooled_axis, k_slices, DeviceVolume, AXIS_DIMS)     # noqa: F401
 from .similarity import sample_features3d, compute_similarities, assign_labels                    # noqa: F401

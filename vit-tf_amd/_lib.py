@@ -33,6 +33,10 @@ class PosEmbed(C.Structure):
     _fields_ = [('cls_plus_pos0', C.c_void_p), ('patch_pos', C.c_void_p)]
 
 
+class RopeTable(C.Structure):
+    _fields_ = [('cos', C.c_void_p), ('sin', C.c_void_p), ('patches', C.c_int32)]
+
+
 class SliceView(C.Structure):
     _fields_ = [('vol', C.c_void_p), ('stride_slice', C.c_int64), ('stride_row', C.c_int64),
                 ('stride_col', C.c_int64), ('in_rows', C.c_int32), ('in_cols', C.c_int32),
@@ -66,6 +70,8 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_vit_qkv_features_reg': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
                                              _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_vit_qkv_features_rope': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
+                                              _vp, _i32, _P(RopeTable), _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_profiler_enable': (C.c_int, [_i32]),
     'vittf_profiler_collect': (C.c_int, [_P(C.c_double), _P(_i64)]),
     'vittf_profiler_kernel_name': (C.c_char_p, [_i32]),
@@ -81,6 +87,7 @@ SIGNATURES = {
     'vittf_block_tail': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     'vittf_gemm_as_workspace_bytes': (_sz, []),
     'vittf_gemm_as': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'vittf_rope_qk': (C.c_int, [_vp, _i64, _i32, _i32, _i32, _P(RopeTable), _i32, _vp]),
     'vittf_attention': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     'vittf_attention_rescale_count': (_i64, [_i32]),
     'vittf_attention_fp8_workspace_bytes': (_sz, [_i32, _i32, _i32]),

@@ -106,12 +106,17 @@ extern "C" size_t vittf_vit_workspace_bytes(const vittf_vit_config* cfg, int32_t
 // n_reg register tokens (DINOv2 _reg models) sit behind CLS in every slice: rows 1 .. n_reg of the residual stream are
 // reg_rows ([n_reg][D] fp32, no position embedding), they take part in every block like any token, and they leave with CLS
 // in the K-feature epilogue.  n_reg = 0 is the plain layout.
-extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
-                                          const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
-                                          const float* reg_rows, int32_t n_reg, uint16_t* q_out, uint16_t* k_out,
-                                          uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
+//
+// rope (DINOv3; NULL: none): the q and k thirds of the patch tokens are rotated in place behind the qkv projection of every full
+// block (rope.hip), inside the qkv profiler scope; the last block's hooked projection is taken before the rotation and never
+// sees it.  The fp8 path quantises q and k inside the GEMM epilogue, before a rotation could happen: refused.
+extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                           const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                           const float* reg_rows, int32_t n_reg, const vittf_rope_table* rope, uint16_t* q_out,
+                                           uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
   if (!config_ok(cfg) || !w || !pos || !view || !ws || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
   if (n_reg < 0 || n_reg > VITTF_MAX_REGISTER_TOKENS || (n_reg > 0 && !reg_rows)) return VITTF_ERR_INVALID_ARG;
+  if (rope && (cfg->attention_fp8 || !rope->cos || !rope->sin)) return VITTF_ERR_INVALID_ARG;
   if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
   if (((part_mask & 1) && !q_out) || ((part_mask & 2) && !k_out) || ((part_mask & 4) && !v_out)) return VITTF_ERR_INVALID_ARG;
   if (!w->qkv_w || !w->qkv_b || !w->proj_w || !w->proj_b || !w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b ||
@@ -121,6 +126,7 @@ extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vit
   if (view->out_rows % p || view->out_cols % p) return VITTF_ERR_INVALID_ARG;
   const int tokens = (view->out_rows / p) * (view->out_cols / p) + 1 + n_reg;
   const int64_t rows = (int64_t)batch * tokens;
+  if (rope && rope->patches != tokens - 1 - n_reg) return VITTF_ERR_INVALID_ARG;
   // the GEMM kernels index a call's widest buffer -- [rows][4 D] 16-bit hidden values, [rows][3 D] on the block-tail path -- with
   // 32-bit element offsets: a batch beyond that is refused, not computed wrong (ViT-B/8 at N = 4097: 341 slices)
   if (rows * (int64_t)((d == 384 && w->tail_packed) ? 3 * d : 4 * d) > 0xffffffffll) return VITTF_ERR_INVALID_ARG;
@@ -173,7 +179,8 @@ extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vit
                            pre ? VITTF_EPI_BIAS_QKV : VITTF_EPI_BIAS, dt, base + lay.tile_ctr, stream);
       else
         rc = vittf_gemm(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, QKV, rows, 3 * d, d,
-                        pre ? VITTF_EPI_BIAS_QKV : VITTF_EPI_BIAS, 0, dt, stream); }
+                        pre ? VITTF_EPI_BIAS_QKV : VITTF_EPI_BIAS, 0, dt, stream);
+      if (!rc && rope) rc = vittf_rope_qk(QKV, rows, tokens, 1 + n_reg, cfg->heads, rope, dt, stream); }
     if (rc) return rc;
     { ProfScope ps(VITTF_KERNEL_ATTENTION, stream);
       if (fp8_rows)
@@ -222,6 +229,14 @@ extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vit
     if (rc) return rc;
   }
   return VITTF_OK;
+}
+
+extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                          const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                          const float* reg_rows, int32_t n_reg, uint16_t* q_out, uint16_t* k_out,
+                                          uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
+  return vittf_vit_qkv_features_rope(cfg, w, pos, view, slice0, batch, part_mask, reg_rows, n_reg, nullptr, q_out, k_out, v_out, ws,
+                                     ws_bytes, stream);
 }
 
 extern "C" int vittf_vit_qkv_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,

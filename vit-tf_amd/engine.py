@@ -10,8 +10,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .weights import (arch_of, fold_layer_scale, fold_patch_embed, interpolate_pos_embed, pack_block_tail_weights,
-                      pack_row_images, pos_embed_antialias_of, register_tokens_of)
+from .weights import (DINOV3_LN_EPS, arch_of, dinov3_canonical, fold_layer_scale, fold_patch_embed, interpolate_pos_embed,
+                      is_dinov3, pack_block_tail_weights, pack_row_images, pos_embed_antialias_of, register_tokens_of,
+                      rope_table)
 
 _TORCH_DT = {_lib.BF16: torch.bfloat16, _lib.FP16: torch.float16}
 
@@ -29,14 +30,18 @@ class _Block:
 class HipViT:
     """Weights + workspace of one ViT on one GPU.
 
-    state_dict: DINO-layout tensors (fp32, CPU or GPU; DINOv2's LayerScale gammas are folded in).  arch: DINO / DINOv2 name
-    ('vits8', 'vits14', 'vits14_reg', ...) or
+    state_dict: DINO-layout tensors (fp32, CPU or GPU; DINOv2's LayerScale gammas are folded in).  arch: DINO / DINOv2 / DINOv3
+    name ('vits8', 'vits14', 'vits14_reg', 'dinov3_vits16', ...) or
     (embed_dim, depth, heads, patch).  A ``register_tokens`` key (1, R, D) makes it a register model (the DINOv2 ``_reg`` names
     require it, a tuple arch follows the key): ``num_register_tokens`` = R rows behind CLS in every slice, kept on the device,
     and the size-based antialiased position-embedding resize.  dtype of the MFMA operands: 'fp16' (default: the reference's own GPU autocast
     type, infer.py:309; meets the 1e-3 parity bound against the fp32 CPU path) or 'bf16' (opt-in: 8-bit mantissa,
     2.4e-3 .. 3.9e-3 against the CPU path).  attention: '16bit' (default) or 'fp8' -- BASELINE configs[3]'s fp8 MFMA
     attention path (e4m3 operands on the block-scaled matrix instruction; ~3e-2 on the features: opt-in).
+    A DINOv3 model ('dinov3_vits16', ...; a tuple arch with a state dict without ``pos_embed``): LayerNorm eps 1e-5, the key
+    bias zeroed, no additive position embedding, and the rotary table of the image size (``rope_for``) handed to the engine,
+    which rotates q and k of the patch tokens in every block; attention='fp8' is refused for it (ValueError): that path
+    quantises q and k inside the qkv GEMM, before the rotation.
     fused_tail=False: ViT-S without the packed weight streams (the block tail and the activation-stationary qkv GEMM): the GEMM
     launches every other width uses; flags: _lib.CFG_* bits (vittf_vit_config.flags), the slower alternatives the tests also run.
     """
@@ -54,9 +59,15 @@ class HipViT:
         if attention not in ('16bit', 'fp8'):
             raise ValueError(f"attention must be '16bit' or 'fp8', got {attention!r}")
         self.attention = attention
-        self.cfg = _lib.VitConfig(dim, depth, heads, patch, self.dtype_id, 1e-6, 1 if attention == 'fp8' else 0, int(flags))
-
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items()}
+        self.rope = is_dinov3(arch, sd)
+        if self.rope:
+            if attention == 'fp8':
+                raise ValueError('attention=\'fp8\' is not available for DINOv3: q and k are quantised inside the qkv GEMM, before '
+                                 'the rotary embedding could be applied')
+            sd = dinov3_canonical(sd)
+        self.cfg = _lib.VitConfig(dim, depth, heads, patch, self.dtype_id, DINOV3_LN_EPS if self.rope else 1e-6,
+                                  1 if attention == 'fp8' else 0, int(flags))
         self.num_register_tokens = register_tokens_of(arch, sd)
         self._pos_antialias = pos_embed_antialias_of(arch, sd)
         # DINOv2 LayerScale (blocks.{i}.ls1 / ls2.gamma present, whatever the arch name): folded into attn.proj / mlp.fc2 in
@@ -89,8 +100,9 @@ class HipViT:
         # [R][D] fp32 rows the embedding kernels copy behind CLS (no position embedding)
         self._reg = sd['register_tokens'].reshape(-1, dim).to(dev).contiguous() if self.num_register_tokens else None
         self._cls = sd['cls_token'].reshape(1, 1, dim)
-        self._pos = sd['pos_embed']
+        self._pos = None if self.rope else sd['pos_embed']
         self._pos_cache = {}
+        self._rope_cache = {}
         self._ws = None
 
     # -- reference-shaped conveniences --------------------------------------------------------------
@@ -104,12 +116,28 @@ class HipViT:
     def pos_for(self, rows, cols):
         """Device position embedding for a rows x cols image: (PosEmbed struct, keep-alive tensors)."""
         key = (rows, cols)
+        if key not in self._pos_cache and self.rope:
+            # DINOv3: nothing is added to the patches (x + 0 keeps the bits) and CLS is the bare cls_token
+            cls0 = self._cls[0, 0].to(self.device).contiguous()
+            patch = torch.zeros((rows // self.patch_size) * (cols // self.patch_size), self.embed_dim, device=self.device)
+            self._pos_cache[key] = (_lib.PosEmbed(cls0.data_ptr(), patch.data_ptr()), cls0, patch)
         if key not in self._pos_cache:
             pos = interpolate_pos_embed(self._pos, rows, cols, self.patch_size, antialias=self._pos_antialias)[0]      # (1 + n, D)
             cls0 = (self._cls[0, 0] + pos[0]).to(self.device).contiguous()
             patch = pos[1:].to(self.device).contiguous()
             self._pos_cache[key] = (_lib.PosEmbed(cls0.data_ptr(), patch.data_ptr()), cls0, patch)
         return self._pos_cache[key]
+
+    def rope_for(self, rows, cols):
+        """DINOv3: the device rotary table for a rows x cols image, (RopeTable struct, keep-alive tensors), computed once per
+        image size in fp32 on the host (weights.rope_table); None for a model without rotary embedding."""
+        if not self.rope:
+            return None
+        key = (rows, cols)
+        if key not in self._rope_cache:
+            cos, sin = (t.to(self.device).contiguous() for t in rope_table(rows // self.patch_size, cols // self.patch_size))
+            self._rope_cache[key] = (_lib.RopeTable(cos.data_ptr(), sin.data_ptr(), cos.shape[0]), cos, sin)
+        return self._rope_cache[key]
 
     def workspace(self, batch, tokens):
         """The engine's workspace for `batch` slices of `tokens` tokens (registers included; grown on demand, kept)."""
@@ -145,10 +173,12 @@ class HipViT:
                 out.numel() >= batch * npatch * self.embed_dim
             ptrs[int(part)] = _lib.ptr(out)
         mask = sum(1 << int(part) for part in outs)
-        rc = self.lib.vittf_vit_qkv_features_reg(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
-                                                 slice0, batch, mask, _lib.ptr(self._reg), self.num_register_tokens, *ptrs,
-                                                 _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, 'vittf_vit_qkv_features_reg')
+        rope = self.rope_for(view.out_rows, view.out_cols)
+        rc = self.lib.vittf_vit_qkv_features_rope(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
+                                                  slice0, batch, mask, _lib.ptr(self._reg), self.num_register_tokens,
+                                                  C.byref(rope[0]) if rope else None, *ptrs, _lib.ptr(ws), ws.numel(),
+                                                  _lib.stream_ptr())
+        _lib.check(rc, 'vittf_vit_qkv_features_rope')
 
     def __call__(self, *_a, **_k):
         raise _lib.VittfError('HipViT is driven through compute_qkv / FeatureExtractor, not called on image tensors')

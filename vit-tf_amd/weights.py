@@ -23,6 +23,23 @@ afterwards and get none.  The stored grid is resized to the token grid by SIZE w
 registers take part in the attention of every block and are dropped, with CLS, from the hooked q / k / v.  No ``_reg``
 checkpoint has been run through this code yet (none was available): the tests use synthetic weights in that layout.
 ViT-g/14 (with or without registers) is not built.
+
+DINOv3 (``dinov3_vits16``, ``dinov3_vitb16``, ``dinov3_vitl16``; restated, nothing vendored; checked against
+``transformers.models.dinov3_vit`` by tests/test_dinov3_cpu.py): patch 16, 4 register tokens behind CLS, LayerScale blocks
+like DINOv2, LayerNorm eps 1e-5, q and v biases but NO key bias, and no additive position embedding -- the state dict has no
+``pos_embed``.  Instead the q and k vectors of the patch tokens are rotated in every block (rotary position embedding, RoPE;
+``rope_table`` below, csrc/rope.hip); CLS and the registers are not.  Two key layouts are read:
+
+* the Hugging Face one (``embeddings.*``, ``layer.{i}.attention.{q,k,v,o}_proj``, ``mlp.up_proj / down_proj``,
+  ``layer_scale{1,2}.lambda1``), converted by ``dinov3_from_hf``; checked against the real class;
+* Meta's own ``.pth`` layout, UNCHECKED (no such file has been available; written from memory): the DINOv2 names with the
+  registers as ``storage_tokens`` (1, 4, D), a full-width ``attn.qkv.bias`` whose k third is masked to zero at run time by the
+  buffer ``blocks.{i}.attn.qkv.bias_mask``, the buffer ``rope_embed.periods``, and no ``pos_embed``.  The loader takes
+  ``storage_tokens`` or ``register_tokens``, zeroes the k third of the bias whatever the file holds, and ignores
+  ``mask_token``, ``rope_embed.*`` and ``*.bias_mask``.  The file names of those checkpoints carry hashes that could not be
+  checked either, so HUB_FILES has no entry for them: weights come from ``--weights``, ``$VITTF_WEIGHTS`` or the synthetic recipe.
+
+``vits16plus`` / ``vith16plus`` (gated SwiGLU MLP, D = 1280 for the latter) and ``vit7b16`` (D = 4096, head dim 128) are not built.
 """
 import math
 import os
@@ -44,10 +61,19 @@ ARCHS = {
     'vits14_reg': (384, 12, 6, 14),
     'vitb14_reg': (768, 12, 12, 14),
     'vitl14_reg': (1024, 24, 16, 14),
+    # dinov3_<name>: patch 16, DINOV3_REGISTER_TOKENS registers, rotary position embedding, no pos_embed (module docstring).
+    # The prefix keeps them apart from DINO's vits16 / vitb16.
+    'dinov3_vits16': (384, 12, 6, 16),
+    'dinov3_vitb16': (768, 12, 12, 16),
+    'dinov3_vitl16': (1024, 24, 16, 16),
 }
 DINOV2_ARCHS = ('vits14', 'vitb14', 'vitl14', 'vits14_reg', 'vitb14_reg', 'vitl14_reg')
 # name: register tokens behind CLS (the state dict's ``register_tokens`` is (1, R, D)); every other name has none
 REGISTER_TOKENS = {'vits14_reg': 4, 'vitb14_reg': 4, 'vitl14_reg': 4}
+DINOV3_ARCHS = ('dinov3_vits16', 'dinov3_vitb16', 'dinov3_vitl16')
+DINOV3_REGISTER_TOKENS = 4              # every DINOv3 name
+DINOV3_LN_EPS = 1e-5                    # DINO and DINOv2: 1e-6
+ROPE_THETA = 100.0
 MAX_REGISTER_TOKENS = 8                 # what the engine's *_reg entry points take (VITTF_MAX_REGISTER_TOKENS)
 DINOV2_STORED_GRID = 37                 # 518 / 14
 # file names torch.hub would have cached for these entries
@@ -87,7 +113,7 @@ def register_tokens_of(arch, state_dict):
             raise ValueError(f'register_tokens has shape {tuple(reg.shape)}, expected (1, R, {arch_of(arch)[0]})')
         have = int(reg.shape[1])
     if isinstance(arch, str):
-        want = REGISTER_TOKENS.get(arch, 0)
+        want = DINOV3_REGISTER_TOKENS if arch in DINOV3_ARCHS else REGISTER_TOKENS.get(arch, 0)
         if have != want:
             raise ValueError(f'{arch} has {want} register tokens, the state dict has {have}'
                              + (' (no register_tokens key)' if reg is None else ''))
@@ -103,12 +129,99 @@ def pos_embed_antialias_of(arch, state_dict):
     return register_tokens_of(arch, state_dict) > 0
 
 
+def is_dinov3(arch, state_dict):
+    """True for a DINOv3 model (rotary position embedding, eps 1e-5, no key bias): a DINOV3_ARCHS name, whose state dict must
+    then have no ``pos_embed``; any other name must have one (a checkpoint of the other family is refused); an arch given as
+    a tuple follows the absence of ``pos_embed``."""
+    has_pos = 'pos_embed' in state_dict
+    if isinstance(arch, str):
+        v3 = arch in DINOV3_ARCHS
+        if v3 and has_pos:
+            raise ValueError(f'{arch} has no additive position embedding, the state dict has a pos_embed: not a DINOv3 checkpoint')
+        if not v3 and not has_pos:
+            raise ValueError(f'{arch} needs a pos_embed, the state dict has none (a DINOv3 checkpoint?)')
+        return v3
+    return not has_pos
+
+
+def dinov3_canonical(sd):
+    """A DINOv3 state dict (Meta-style or already canonical; Hugging Face files go through dinov3_from_hf first) as the engine
+    reads it: the registers under ``register_tokens`` (from ``storage_tokens``), the k third of every ``attn.qkv.bias`` zeroed
+    whatever the file holds (upstream masks it at run time), and without ``mask_token``, ``rope_embed.*`` and ``*.bias_mask``.
+    Returns a new dict; the input tensors are not modified."""
+    out = {}
+    for k, v in sd.items():
+        if k == 'mask_token' or k.startswith('rope_embed.') or k.endswith('.bias_mask'):
+            continue
+        if k == 'storage_tokens':
+            k = 'register_tokens'
+        if k.endswith('.attn.qkv.bias'):
+            d = v.shape[0] // 3
+            v = v.clone()
+            v[d:2 * d] = 0
+        out[k] = v
+    return out
+
+
+_HF_BLOCK = (('norm1.', 'norm1.'), ('norm2.', 'norm2.'), ('attention.o_proj.', 'attn.proj.'), ('mlp.up_proj.', 'mlp.fc1.'),
+             ('mlp.down_proj.', 'mlp.fc2.'))
+
+
+def is_dinov3_hf_layout(sd):
+    return 'embeddings.patch_embeddings.weight' in sd and any(k.endswith('attention.q_proj.weight') for k in sd)
+
+
+def dinov3_from_hf(sd):
+    """The Hugging Face DINOv3ViTModel state dict in this project's canonical DINOv3 layout: ``q_proj / k_proj / v_proj``
+    concatenated into ``blocks.{i}.attn.qkv`` with a zero k bias (the class has none), ``o_proj -> attn.proj``,
+    ``up_proj / down_proj -> mlp.fc1 / fc2``, ``layer_scale{1,2}.lambda1 -> ls{1,2}.gamma``, ``embeddings.* -> cls_token /
+    register_tokens / patch_embed.proj.*``, ``layer.{i} -> blocks.{i}`` (with or without the ``model.`` prefix the class puts
+    in front of its encoder).  A gated MLP (``gate_proj``: the ``plus`` models) is refused."""
+    sd = {(k[len('model.'):] if k.startswith('model.layer.') else k): v for k, v in sd.items()}
+    if any('.mlp.gate_proj.' in k for k in sd):
+        raise ValueError('gated (SwiGLU) MLP: the DINOv3 "plus" and 7B models are not supported')
+    out = {'cls_token': sd['embeddings.cls_token'], 'register_tokens': sd['embeddings.register_tokens'],
+           'patch_embed.proj.weight': sd['embeddings.patch_embeddings.weight'],
+           'patch_embed.proj.bias': sd['embeddings.patch_embeddings.bias'],
+           'norm.weight': sd['norm.weight'], 'norm.bias': sd['norm.bias']}
+    i = 0
+    while f'layer.{i}.attention.q_proj.weight' in sd:
+        a, b = f'layer.{i}.', f'blocks.{i}.'
+        wq = sd[a + 'attention.q_proj.weight']
+        out[b + 'attn.qkv.weight'] = torch.cat([wq, sd[a + 'attention.k_proj.weight'], sd[a + 'attention.v_proj.weight']])
+        zero = torch.zeros(wq.shape[0], dtype=wq.dtype)
+        out[b + 'attn.qkv.bias'] = torch.cat([sd.get(a + 'attention.q_proj.bias', zero), zero,
+                                              sd.get(a + 'attention.v_proj.bias', zero)])
+        for theirs, ours in _HF_BLOCK:
+            for p in ('weight', 'bias'):
+                out[b + ours + p] = sd[a + theirs + p]
+        out[b + 'ls1.gamma'] = sd[a + 'layer_scale1.lambda1']
+        out[b + 'ls2.gamma'] = sd[a + 'layer_scale2.lambda1']
+        i += 1
+    if i == 0:
+        raise ValueError('no layer.{i}.attention.q_proj.weight key: not a Hugging Face DINOv3 state dict')
+    return out
+
+
+def rope_table(f0, f1):
+    """(cos, sin), each fp32 [f0 * f1][32]: DINOv3's rotary table for an f0 x f1 patch grid, head dim 64 -- the 32 distinct
+    angles of a patch (columns j and j + 32 of a head share angle j).  fp32 and this order of operations throughout: the table
+    is then bit-equal to transformers' DINOv3ViTRopePositionEmbedding (first 32 columns; tests/test_dinov3_cpu.py), while
+    ``theta ** -(i / 16)`` for inv_freq is already 1 ulp off.  Depends on the grid only: computed once per image size."""
+    inv_freq = 1 / ROPE_THETA ** torch.arange(0, 1, 1 / 16, dtype=torch.float32)                 # 16 values
+    cy = 2.0 * (torch.arange(0.5, f0, dtype=torch.float32) / f0) - 1.0
+    cx = 2.0 * (torch.arange(0.5, f1, dtype=torch.float32) / f1) - 1.0
+    coords = torch.stack(torch.meshgrid(cy, cx, indexing='ij'), dim=-1).flatten(0, 1)           # (f0 f1, 2): (y, x)
+    angles = (2 * math.pi * coords[:, :, None] * inv_freq[None, None, :]).flatten(1, 2)        # (f0 f1, 32)
+    return torch.cos(angles).contiguous(), torch.sin(angles).contiguous()
+
+
 # "massive activation" channels of the outlier variant below (trained ViTs carry a handful of residual-stream channels two
 # orders of magnitude above the rest; Gaussian unit-gain weights have none)
 OUTLIER_CHANNELS = (7, 100, 191, 250, 333, 380)
 
 
-def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False, layer_scale=None):
+def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False, layer_scale=None, dinov3=None):
     """Seeded random weights with the DINO key layout.
 
     stored_grid: side of the stored position-embedding grid (default 28, 37 for the DINOv2 names).
@@ -117,6 +230,11 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False,
     their own, after every DINO tensor, so the DINO tensors of a seed do not depend on this flag.  The ``_reg`` names add
     ``register_tokens`` (1, R, D), std 0.5, from a third generator after all of those: ``vits14_reg`` and ``vits14`` of one
     seed agree on every shared key.
+
+    dinov3 (default: True for the DINOV3_ARCHS names only; pass True with a tuple arch): Meta's DINOv3 key layout as far as it
+    is known (module docstring) -- the DINO tensors of the seed without ``pos_embed``, the LayerScale keys, the registers as
+    ``storage_tokens`` (1, 4, D) from the register generator, ``rope_embed.periods``, and per block a ``attn.qkv.bias_mask``
+    (1 / 0 / 1 over the thirds) beside a bias whose k third is NOT zero: a loader that forgets the mask gives other features.
 
     outliers=True: the same weights with six massive channels planted -- x50 rows in two blocks' mlp.fc2 and one block's
     attn.proj (the residual stream then carries them to the end), x50 entries in several norm weights (16-bit LayerNorm
@@ -131,6 +249,10 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False,
     """
     dim, depth, heads, patch = arch_of(arch)
     dinov2 = isinstance(arch, str) and arch in DINOV2_ARCHS
+    if dinov3 is None:
+        dinov3 = isinstance(arch, str) and arch in DINOV3_ARCHS
+    if layer_scale is None and dinov3:
+        layer_scale = True
     if stored_grid is None:
         stored_grid = DINOV2_STORED_GRID if dinov2 else 28
     if layer_scale is None:
@@ -188,9 +310,18 @@ def synthetic_state_dict(arch='vits8', seed=0, stored_grid=None, outliers=False,
             for ls in ('ls1', 'ls2'):
                 sd[f'blocks.{i}.{ls}.gamma'] = 10.0 ** (torch.rand(dim, generator=g2) * -5.0)
     n_reg = REGISTER_TOKENS.get(arch, 0) if isinstance(arch, str) else 0
+    if dinov3:
+        n_reg = DINOV3_REGISTER_TOKENS
     if n_reg:
         g3 = torch.Generator().manual_seed(0x4e6157 + seed)
-        sd['register_tokens'] = torch.randn(1, n_reg, dim, generator=g3) * 0.5
+        sd['storage_tokens' if dinov3 else 'register_tokens'] = torch.randn(1, n_reg, dim, generator=g3) * 0.5
+    if dinov3:
+        del sd['pos_embed']
+        sd['rope_embed.periods'] = ROPE_THETA ** torch.arange(0, 1, 1 / 16, dtype=torch.float32)
+        mask = torch.ones(3 * dim)
+        mask[dim:2 * dim] = 0
+        for i in range(depth):
+            sd[f'blocks.{i}.attn.qkv.bias_mask'] = mask.clone()
     return sd
 
 
@@ -215,8 +346,19 @@ def fold_layer_scale(sd):
 
 
 def load_state_dict_file(path):
-    """Load a DINO checkpoint from a local file; accepts bare backbones and teacher/student wrappers."""
-    sd = torch.load(path, map_location='cpu', weights_only=True)
+    """Load a DINO / DINOv2 / DINOv3 checkpoint from a local file; accepts bare backbones and teacher/student wrappers.  A
+    ``.safetensors`` file is read with the ``safetensors`` module (absent: a message and exit code 1).  The Hugging Face DINOv3
+    layout is recognised by its keys and converted (dinov3_from_hf)."""
+    if str(path).endswith('.safetensors'):
+        try:
+            from safetensors.torch import load_file
+        except ImportError:
+            print(f'{path}: reading .safetensors needs the safetensors module, which is not installed. '
+                  'Convert the file to a torch state dict (.pth) or install safetensors.')
+            raise SystemExit(1)
+        sd = load_file(str(path), device='cpu')
+    else:
+        sd = torch.load(path, map_location='cpu', weights_only=True)
     for key in ('teacher', 'student', 'state_dict', 'model'):
         if isinstance(sd, dict) and key in sd and isinstance(sd[key], dict):
             sd = sd[key]
@@ -229,6 +371,8 @@ def load_state_dict_file(path):
         if k.startswith('head.'):
             continue
         out[k] = v.float()
+    if is_dinov3_hf_layout(out):
+        out = dinov3_from_hf(out)
     return out
 
 
