@@ -184,6 +184,24 @@ int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vittf_vit_wei
                                 const float* reg_rows, int32_t n_reg, const vittf_rope_table* table, uint16_t* q_out,
                                 uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream);
 
+/* The whole feature call: vittf_vit_qkv_features_rope plus the TOKEN facet, the final-norm patch tokens the DINOv2 / DINOv3
+ * families publish as their dense feature (x_norm_patchtokens, get_intermediate_layers(norm=True); last_hidden_state[:, 1 + R:]
+ * in transformers).  part_mask bits 0..2 = q, k, v of the hooked projection of block cfg->depth - 1, as before; bit 3 (8) = the
+ * token facet: block cfg->depth - 1 is run in full, then the model's final LayerNorm norm_g / norm_b (fp32 [D], cfg->ln_eps)
+ * over the patch-token rows of the fp32 residual stream (vittf_token_features); CLS and the n_reg register rows are dropped.
+ * t_out: fp16 [batch][f0*f1][D], the layout of the other three outputs; fp16 whatever cfg->dtype, rounded once.  All four facets
+ * come from ONE forward: with bit 3 and any of bits 0..2, the hooked thirds leave first (before the rotation, without the q
+ * pre-scale: the bits of a call without bit 3), then the block goes on.  A hooked block in the middle of the model: set
+ * cfg->depth to its index + 1 and pass the whole weight stacks; the final norm is then applied to that block's output.  Without
+ * bit 3 this is vittf_vit_qkv_features_rope, bit for bit and launch for launch (norm_g, norm_b, t_out ignored, may be NULL).
+ * part_mask outside 1..15, a NULL output of a set bit, bit 3 with a NULL norm_g / norm_b: VITTF_ERR_INVALID_ARG.  Workspace,
+ * batch limit and every other check as vittf_vit_qkv_features_rope.  cfg->attention_fp8 without a table is allowed.
+ * [host] cfg, w, pos, view, table are host structs holding device pointers. */
+int vittf_vit_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                       const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask, const float* reg_rows,
+                       int32_t n_reg, const vittf_rope_table* table, const float* norm_g, const float* norm_b, uint16_t* q_out,
+                       uint16_t* k_out, uint16_t* v_out, uint16_t* t_out, void* ws, size_t ws_bytes, void* stream);
+
 /* Optional timing of the launches inside vittf_vit_k_features and vittf_similarity, by kernel class, with HIP events recorded on
  * the caller's stream (what bench.py's roofline leg reads).  Process-global, off by default, not thread-safe:
  * the one exception to "no global mutable state".  enable(mask) clears earlier records and starts recording the
@@ -226,6 +244,14 @@ int vittf_patch_embed_reg(const vittf_vit_config* cfg, const vittf_vit_weights* 
 /* y = LayerNorm(x) * g + b, x fp32 [rows][D] -> y h16 [rows][D]  (nn.LayerNorm, biased variance) */
 int vittf_layernorm(const float* x, const float* g, const float* b, void* y, int64_t rows, int32_t d,
                     float eps, int32_t dtype, void* stream);
+
+/* The token facet's output kernel: t_out[b * (tokens - prefix) + t][d] (fp16) = LayerNorm(x[b * tokens + prefix + t]; norm_g,
+ * norm_b, eps) for b < batch, t < tokens - prefix; x fp32 [batch * tokens][d], 16-byte aligned like norm_g and norm_b; t_out
+ * 8-byte aligned.  The first `prefix` (>= 1: CLS + register tokens) rows of every slice are skipped, not read.  Statistics and
+ * the affine map in fp32, biased variance as nn.LayerNorm, one rounding to fp16.  d a multiple of 4, at most 1024.  A row's bits
+ * do not depend on batch or on where the slice sits in x. */
+int vittf_token_features(const float* x, const float* norm_g, const float* norm_b, uint16_t* t_out, int32_t batch,
+                         int32_t tokens, int32_t prefix, int32_t d, float eps, void* stream);
 
 typedef enum vittf_epilogue {
   VITTF_EPI_BIAS = 0,        /* out h16 [rows][n] = a.w^T + bias */

@@ -12,6 +12,10 @@ Differences a caller can observe:
     fetched from the network (the reference calls torch.hub.load, :42-43)
   * ``--batch-size`` no longer changes memory behaviour: slices are independent and the engine picks its
     own batch (results do not depend on it); ``--engine-dtype`` selects fp16 (default, the reference's autocast type :309) or bf16 MFMA operands
+  * ``--facet {key,query,value,token}`` picks what is saved (default ``key``, the reference's): a third of the hooked qkv
+    projection, or ``token`` -- the model's final-norm patch tokens, the dense feature DINOv2 / DINOv3 publish
+    (x_norm_patchtokens); ``--layer N`` hooks block N (0-based, negatives from the end) instead of the last one.  The file's
+    dict key is the facet's letter (q, k, v, t); a non-default facet or layer is appended to the default file name
   * launched under torchrun, the slices of each axis are sharded over the ranks and reassembled with one
     RCCL all-gather per axis; rank 0 writes the file
 """
@@ -61,7 +65,8 @@ def norm_mean_std(t, mu=0, std=1):
 
 
 # ---------------------------------------------------------------------------- model (:42-46, :239-264)
-_MODEL_OPTS = {'weights': None, 'synthetic_seed': None, 'dtype': 'fp16', 'attention': '16bit'}
+_MODEL_OPTS = {'weights': None, 'synthetic_seed': None, 'dtype': 'fp16', 'attention': '16bit', 'layer': None}
+FACETS = {'key': 'k', 'query': 'q', 'value': 'v', 'token': 't'}     # --facet -> the saved dict's key (vt.extract.PARTS)
 
 
 def _engine_model(name, hub):
@@ -80,7 +85,7 @@ def _engine_model(name, hub):
         print(f'No local checkpoint for {name if name.startswith(hub) else hub + "_" + name}: pass --weights PATH ({hub.upper()} state dict) or '
               f'--synthetic-weights SEED. This build never downloads weights.')
         sys.exit(1)
-    return vt.HipViT(sd, name, dtype=_MODEL_OPTS['dtype'], attention=_MODEL_OPTS['attention'])
+    return vt.HipViT(sd, name, dtype=_MODEL_OPTS['dtype'], attention=_MODEL_OPTS['attention'], layer=_MODEL_OPTS['layer'])
 
 
 def get_dino_model(name):
@@ -167,7 +172,8 @@ def _noop(x, **kwargs):
 # ---------------------------------------------------------------------------- extraction (:130-210)
 def compute_qkv(vol, model, patch_size, im_sizes, pool_fn=_noop, batch_size=1, slice_along='z',
                 return_keys=['q', 'k', 'v'], dev=None, typ=None, group=None):
-    """(:130-210) features of the last block's qkv projection for every slice of one axis.
+    """(:130-210) features of the hooked block's qkv projection for every slice of one axis; `return_keys` also takes 't',
+    the final-norm patch tokens behind that block (all requested keys from one pass).
 
     Returns {key: CPU tensor} with, like the reference, (F, W', H', S)-style un-pooled layout for
     ``pool_fn=_noop`` and the pooled (F, *output_size) volume when ``pool_fn`` is an
@@ -230,6 +236,15 @@ def handle_output_path(args):
     data_path = Path(args.data_path)
     if not args.cache_path:
         stem = f'{data_path.stem}_{args.model.replace("/", "_")}_{args.slice_along}_features{args.feature_output_size}'
+        # a non-default facet / hooked block is named; the default run keeps the reference's file name
+        facet, layer = getattr(args, 'facet', 'key'), getattr(args, 'layer', -1)
+        if facet != 'key':
+            stem += f'_{facet}'
+        if layer is not None and layer != -1:
+            depth = vt.weights.arch_of(args.model)[1]
+            idx = vt.engine.resolve_layer(layer, depth)
+            if idx != depth - 1:
+                stem += f'_L{idx}'
         args.cache_path = data_path.parent / f'{stem}{data_path.suffix}'
     cache_path = Path(args.cache_path)
     if cache_path.exists() and not args.overwrite:
@@ -242,7 +257,7 @@ def handle_output_path(args):
 
 
 def save_features(qkv, cache_path):
-    """(:337-340) {'k': fp16 (F, W', H', D')} as .pt (torch.save) or .npy (pickled dict)."""
+    """(:337-340) {'k': fp16 (F, W', H', D')} (or 'q' / 'v' / 't', --facet) as .pt (torch.save) or .npy (pickled dict)."""
     cache_path = Path(cache_path)
     if cache_path.suffix in ('.pt', '.pth'):
         torch.save(qkv, cache_path)
@@ -316,6 +331,10 @@ def main(argv=None):
                         help='MFMA operand type (fp16 = the reference GPU autocast type, 1e-3 parity; bf16 opt-in)')
     parser.add_argument('--attention', type=str, choices=['16bit', 'fp8'], default='16bit',
                         help="fp8: e4m3 attention on the block-scaled matrix instruction (BASELINE configs[3]; ~3e-2 on the features)")
+    parser.add_argument('--facet', type=str, choices=list(FACETS), default='key',
+                        help='what to save: key / query / value = that third of the hooked qkv projection (key: the reference), '
+                        'token = the final-norm patch tokens behind the hooked block (x_norm_patchtokens of DINOv2 / DINOv3)')
+    parser.add_argument('--layer', type=int, default=-1, help='hooked block, 0-based; negatives count from the end (default -1: the last block)')
     args = parser.parse_args(argv)
 
     if args.cpu:
@@ -323,6 +342,13 @@ def main(argv=None):
         sys.exit(1)
     _MODEL_OPTS.update(weights=args.weights, synthetic_seed=args.synthetic_weights, dtype=args.engine_dtype, attention=args.attention)
     dino_model, dino_model_fn, patch_size = load_model(args)
+    if args.model in vt.ARCHS:             # (a model the engine refuses says so itself, in dino_model_fn)
+        try:
+            vt.engine.resolve_layer(args.layer, vt.ARCHS[args.model][1])
+        except ValueError as e:
+            print(f'Invalid argument for --layer: {e}')
+            sys.exit(1)
+    _MODEL_OPTS['layer'] = args.layer
     rank, world = _init_distributed()
     cache_path = _agree_on_output_path(args, rank, world)
 
@@ -333,14 +359,15 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.time()
     eb = vt.extract.AtLeast(args.batch_size) if args.batch_size > 1 else None   # a lower bound (extract.engine_batch_for)
-    feats = vt.feature_volume(vol, model, args.feature_output_size, args.slice_along, eb)
+    key = FACETS[args.facet]
+    feats = vt.feature_volume(vol, model, args.feature_output_size, args.slice_along, eb, part=vt.extract.PARTS[key])
     if args.slice_along == 'all':
         qkv = defaultdict(float)           # the reference saves a defaultdict in 'all' mode (:328)
-        qkv['k'] = feats.cpu()
+        qkv[key] = feats.cpu()
     else:
-        qkv = {'k': feats.cpu()}
+        qkv = {key: feats.cpu()}
     if rank == 0:
-        print('k', ':', qkv['k'].shape)
+        print(key, ':', qkv[key].shape)
         print(f'Computed qkv along {args.slice_along} in {time.time() - t0}s, saving now to: {cache_path}')
         save_features(qkv, cache_path)
     if world > 1 or torch.distributed.is_initialized():

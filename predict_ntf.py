@@ -57,6 +57,19 @@ def _metrics(labels, pred, names):
     }
 
 
+def pick_features(features):
+    """The feature volume of a loaded feature file: a bare array, or infer.py's dict -- its 'k' entry when there is one (the
+    reference's layout), else the only entry of a one-entry dict (infer.py --facet query / value / token)."""
+    if isinstance(features, dict):
+        if 'k' in features:
+            features = features['k']
+        elif len(features) == 1:
+            features = next(iter(features.values()))
+        else:
+            raise ValueError(f"feature file holds {sorted(features)}: expected a 'k' entry or exactly one entry")
+    return torch.as_tensor(features).squeeze()
+
+
 def main(argv=None):
     parser = ArgumentParser()
     parser.add_argument('--data', type=str, help='directory holding volume, features and annotations / labels')
@@ -90,7 +103,7 @@ def main(argv=None):
     else:
         assert args.num_samples == 0.0, 'Cannot sample labels if they are not provided'
     features = np.load(feat_fn, allow_pickle=True)[()]
-    features = torch.as_tensor(features['k'] if isinstance(features, dict) else features).squeeze()
+    features = pick_features(features)
 
     if args.num_samples == 0.0:
         annotations = np.load(d / 'annotations.npy', allow_pickle=True)[()]

@@ -15,6 +15,12 @@ order, so the models alternate: the line then carries every run's slices/s under
 one model is the yardstick for a difference between two), and each model's entry is its last run.
 ``--archs dinov3_vits16 vits14_reg``: both run N = 4101 at D = 384, so the difference is DINOv3's rotation of q and k (inside
 the ``gemm_qkv`` class) plus the patch-16 against the patch-14 embedding.
+
+--facet {key,query,value,token} / --layer N (infer.py's flags; default key, -1): with a non-default value every model of the
+list is run twice per repeat, at the default and at the chosen facet / layer, as ``<arch>`` and ``<arch>@<facet>[_L<N>]``; the
+line then carries ``<arch>@..._over_<arch>_slices_per_s`` for every model, and one model is enough.  ``--archs vits14_reg
+dinov3_vits16 --facet token``: the cost of the token facet (one more full block and the final-norm kernel for one small
+GEMM less) beside the key facet.
 """
 import argparse
 import json
@@ -27,30 +33,31 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(arch, vol, fos, steps, warmup):
+def run(arch, vol, fos, steps, warmup, facet='key', layer=-1):
     import torch
     import vit_tf_amd as vt
-    model = vt.HipViT(vt.synthetic_state_dict(arch, 0), arch, 'fp16')
+    model = vt.HipViT(vt.synthetic_state_dict(arch, 0), arch, 'fp16', layer=layer)
+    part = vt.extract.PARTS[facet[0]]
     dvol = vt.DeviceVolume(vol, model.device)
     im_sz, feat_out = vt.sizing(dvol.shape, fos, model.patch_size)
     slices = sum(dvol.shape)                   # every slice of every axis runs through the ViT (pooled windows cover them)
     for _ in range(warmup):
-        vt.feature_volume(None, model, fos, 'all', dvol=dvol)
+        vt.feature_volume(None, model, fos, 'all', dvol=dvol, part=part)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        out = vt.feature_volume(None, model, fos, 'all', dvol=dvol)
+        out = vt.feature_volume(None, model, fos, 'all', dvol=dvol, part=part)
     torch.cuda.synchronize()
     sec = (time.perf_counter() - t0) / steps
     vt._lib.profiler_enable(True)
     try:
-        vt.feature_volume(None, model, fos, 'all', dvol=dvol)
+        vt.feature_volume(None, model, fos, 'all', dvol=dvol, part=part)
         torch.cuda.synchronize()
         prof = vt._lib.profiler_collect()
     finally:
         vt._lib.profiler_enable(False)
     ms = {k: round(v[0], 3) for k, v in prof.items() if v[1]}
-    res = {'arch': arch, 'image': list(im_sz),
+    res = {'arch': arch, 'facet': facet, 'layer': model.layer, 'image': list(im_sz),
            'tokens': (im_sz[0] // model.patch_size) * (im_sz[1] // model.patch_size) + 1 + model.num_register_tokens,
            'slices_per_step': slices, 'ms_per_step': round(sec * 1e3, 2), 'slices_per_s': round(slices / sec, 1),
            'class_ms_per_step': ms, 'patch_embed_kernel': vt._lib.kernel_name('patch_embed'),
@@ -69,23 +76,34 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--archs', nargs='+', default=['vits14', 'vits8'], help='models to time, in order (default: vits14 vits8)')
     ap.add_argument('--repeats', type=int, default=1, help='run the list this many times, alternating the models')
+    ap.add_argument('--facet', default='key', choices=['key', 'query', 'value', 'token'], help='facet to time beside the key facet')
+    ap.add_argument('--layer', type=int, default=-1, help='hooked block to time beside the last one (0-based, negatives from the end)')
     args = ap.parse_args()
-    if len(set(args.archs)) != len(args.archs) or len(args.archs) < 2:
-        ap.error('--archs takes two or more different models')
+    variant = args.facet != 'key' or args.layer != -1
+    if len(set(args.archs)) != len(args.archs) or len(args.archs) < (1 if variant else 2):
+        ap.error('--archs takes two or more different models (one or more with --facet / --layer)')
     import torch
     import bench
     import vit_tf_amd as vt
     torch.cuda.set_device(0)
     vol, _, desc = bench.make_workload(args.workload, vt)
-    res, runs = {}, {name: [] for name in args.archs}
+    tag = '@' + args.facet + (f'_L{args.layer}' if args.layer != -1 else '')
+    # (name on the line, model, facet, layer), in running order: with a variant every model runs at the default first
+    plan = []
+    for name in args.archs:
+        plan.append((name, name, 'key', -1))
+        if variant:
+            plan.append((name + tag, name, args.facet, args.layer))
+    res, runs = {}, {key: [] for key, *_ in plan}
     for _ in range(max(1, args.repeats)):
-        for name in args.archs:
-            res[name] = run(name, vol, args.fos, args.steps, args.warmup)
-            runs[name].append(res[name]['slices_per_s'])
-    a, b = args.archs[0], args.archs[1]
+        for key, name, facet, layer in plan:
+            res[key] = run(name, vol, args.fos, args.steps, args.warmup, facet, layer)
+            runs[key].append(res[key]['slices_per_s'])
     line = {'tool': 'dinov2_step', 'workload': args.workload, 'fos': args.fos, 'steps': args.steps,
-            'device': torch.cuda.get_device_name(0), **{name: res[name] for name in args.archs},
-            f'{a}_over_{b}_slices_per_s': round(res[a]['slices_per_s'] / res[b]['slices_per_s'], 4)}
+            'device': torch.cuda.get_device_name(0), **{key: res[key] for key, *_ in plan}}
+    pairs = [(n + tag, n) for n in args.archs] if variant else [(args.archs[0], args.archs[1])]
+    for a, b in pairs:
+        line[f'{a}_over_{b}_slices_per_s'] = round(res[a]['slices_per_s'] / res[b]['slices_per_s'], 4)
     if args.repeats > 1:
         line['runs'] = runs
     print(json.dumps(line))

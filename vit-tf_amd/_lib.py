@@ -72,12 +72,15 @@ SIGNATURES = {
                                              _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_vit_qkv_features_rope': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32,
                                               _vp, _i32, _P(RopeTable), _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_vit_features': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _i32, _vp, _i32,
+                                     _P(RopeTable), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_profiler_enable': (C.c_int, [_i32]),
     'vittf_profiler_collect': (C.c_int, [_P(C.c_double), _P(_i64)]),
     'vittf_profiler_kernel_name': (C.c_char_p, [_i32]),
     'vittf_patch_embed': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _vp, _vp]),
     'vittf_patch_embed_reg': (C.c_int, [_P(VitConfig), _P(VitWeights), _P(PosEmbed), _P(SliceView), _i32, _i32, _vp, _i32, _vp,
                                         _vp]),
+    'vittf_token_features': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp]),
     'vittf_layernorm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, _i32, _vp]),
     'vittf_gemm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     'vittf_gemm_kfeat_parts': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),

@@ -4,6 +4,7 @@
 // forward hook on blocks[-1].attn.qkv (infer.py:133-135, 173-177): patch embed, (L-1) full pre-norm blocks and
 // then only LayerNorm1 + the requested thirds (q, k, v) of the last block's qkv projection, in one launch -- the rest
 // of block L and the final norm never influence the hooked tensor, so they are not executed.
+// The token facet (vittf_vit_features, part_mask bit 3) is the other case: block L in full and the final norm of its patch tokens.
 //
 // Workspace layout for `batch` slices of N tokens (N = f0*f1 + 1 + register tokens; rows = batch * N, padded to the GEMM tile):
 //   X    fp32 [rows][D]      residual stream
@@ -110,15 +111,24 @@ extern "C" size_t vittf_vit_workspace_bytes(const vittf_vit_config* cfg, int32_t
 // rope (DINOv3; NULL: none): the q and k thirds of the patch tokens are rotated in place behind the qkv projection of every full
 // block (rope.hip), inside the qkv profiler scope; the last block's hooked projection is taken before the rotation and never
 // sees it.  The fp8 path quantises q and k inside the GEMM epilogue, before a rotation could happen: refused.
-extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
-                                           const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
-                                           const float* reg_rows, int32_t n_reg, const vittf_rope_table* rope, uint16_t* q_out,
-                                           uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
+//
+// Token facet (part_mask bit 3): the hooked block is run in full like every block in front of it -- its hooked thirds, if any
+// are asked for, leave first, from the same norm1 output -- and the patch-token rows of the residual stream behind it go through
+// the model's final LayerNorm (token_out.hip).  Where the block's last kernel writes "the next block's norm1" on its way, the
+// last executed block is given norm_g / norm_b instead: row depth of the ln1 stacks does not exist.  Without bit 3 nothing of
+// this is launched: the call returns behind the hooked projection as it always did.
+extern "C" int vittf_vit_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                  const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                  const float* reg_rows, int32_t n_reg, const vittf_rope_table* rope, const float* norm_g,
+                                  const float* norm_b, uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, uint16_t* t_out,
+                                  void* ws, size_t ws_bytes, void* stream) {
   if (!config_ok(cfg) || !w || !pos || !view || !ws || batch <= 0 || slice0 < 0) return VITTF_ERR_INVALID_ARG;
   if (n_reg < 0 || n_reg > VITTF_MAX_REGISTER_TOKENS || (n_reg > 0 && !reg_rows)) return VITTF_ERR_INVALID_ARG;
   if (rope && (cfg->attention_fp8 || !rope->cos || !rope->sin)) return VITTF_ERR_INVALID_ARG;
-  if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
+  if (part_mask <= 0 || part_mask > 15) return VITTF_ERR_INVALID_ARG;
   if (((part_mask & 1) && !q_out) || ((part_mask & 2) && !k_out) || ((part_mask & 4) && !v_out)) return VITTF_ERR_INVALID_ARG;
+  const bool want_t = (part_mask & 8) != 0;
+  if (want_t && (!t_out || !norm_g || !norm_b)) return VITTF_ERR_INVALID_ARG;
   if (!w->qkv_w || !w->qkv_b || !w->proj_w || !w->proj_b || !w->fc1_w || !w->fc1_b || !w->fc2_w || !w->fc2_b ||
       !w->ln1_g || !w->ln1_b || !w->ln2_g || !w->ln2_b)
     return VITTF_ERR_INVALID_ARG;
@@ -164,12 +174,16 @@ extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vi
       rc = vittf_layernorm(X, w->ln1_g + (size_t)l * d, w->ln1_b + (size_t)l * d, H, rows, d, cfg->ln_eps, dt, stream);
       if (rc) return rc;
     }
-    if (l == L - 1) {
+    if (l == L - 1 && (part_mask & 7)) {
       // hooked tensor, the requested thirds only: rows [part*D, (part+1)*D) of qkv.weight / qkv.bias  (infer.py:189-209)
       ProfScope ps(VITTF_KERNEL_GEMM, stream);   // the K-feature projection: one launch for every requested third
-      return vittf_gemm_kfeat_parts_reg(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, rows, d, d, tokens, n_reg, part_mask, q_out, k_out,
-                                        v_out, dt, stream);
+      rc = vittf_gemm_kfeat_parts_reg(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, rows, d, d, tokens, n_reg, part_mask & 7, q_out,
+                                      k_out, v_out, dt, stream);
+      if (rc || !want_t) return rc;
     }
+    // the LayerNorm riding on this block's last kernel: the next block's norm1, or the final norm behind the last executed one
+    const float* next_g = l == L - 1 ? norm_g : w->ln1_g + (size_t)(l + 1) * d;
+    const float* next_b = l == L - 1 ? norm_b : w->ln1_b + (size_t)(l + 1) * d;
     { ProfScope ps(VITTF_KERNEL_GEMM_QKV, stream);
       if (fp8_rows)
         rc = vittf_gemm_qkv_fp8(H, qkv_w, w->qkv_b + (size_t)l * 3 * d, QKV, rows, 3 * d, d, tokens, cfg->heads, dt,
@@ -196,8 +210,8 @@ extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vi
       ProfScope ps(VITTF_KERNEL_MLP, stream);
       rc = vittf_block_tail(O, (const char*)w->tail_packed + (size_t)l * VITTF_TAIL_STEPS * 12288 * esz, w->proj_b + (size_t)l * d,
                             w->ln2_g + (size_t)l * d, w->ln2_b + (size_t)l * d, w->fc1_b + (size_t)l * 4 * d,
-                            w->fc2_b + (size_t)l * d, X, rows, d, dt, w->ln1_g + (size_t)(l + 1) * d,
-                            w->ln1_b + (size_t)(l + 1) * d, cfg->ln_eps, H, base + lay.tile_ctr, stream);
+                            w->fc2_b + (size_t)l * d, X, rows, d, dt, next_g, next_b, cfg->ln_eps, H, base + lay.tile_ctr,
+                            stream);
       if (rc) return rc;
       continue;
     }
@@ -219,16 +233,27 @@ extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vi
                       4 * d, d, VITTF_EPI_BIAS_GELU, 0, dt, stream); }
     if (rc) return rc;
     { ProfScope ps(VITTF_KERNEL_GEMM_FC2, stream);
-      if (res_ln)   // (l + 1 < L always holds here: the last block returns above)
+      if (res_ln)
         rc = vittf_gemm_residual_ln(G, (const char*)w->fc2_w + (size_t)l * 4 * d * d * esz, w->fc2_b + (size_t)l * d, X, rows,
-                                    d, 4 * d, dt, w->ln1_g + (size_t)(l + 1) * d, w->ln1_b + (size_t)(l + 1) * d,
-                                    cfg->ln_eps, H, stream);
+                                    d, 4 * d, dt, next_g, next_b, cfg->ln_eps, H, stream);
       else
         rc = vittf_gemm(G, (const char*)w->fc2_w + (size_t)l * 4 * d * d * esz, w->fc2_b + (size_t)l * d, X, rows, d,
                         4 * d, VITTF_EPI_BIAS_RESIDUAL, 0, dt, stream); }
     if (rc) return rc;
   }
-  return VITTF_OK;
+  // only the token facet gets here (every other mask has returned behind the hooked projection)
+  ProfScope ps(VITTF_KERNEL_LAYERNORM, stream);
+  return vittf_token_features(X, norm_g, norm_b, t_out, batch, tokens, 1 + n_reg, d, cfg->ln_eps, stream);
+}
+
+// the hooked thirds only (no token facet, no final norm): the same call, bit for bit
+extern "C" int vittf_vit_qkv_features_rope(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,
+                                           const vittf_slice_view* view, int32_t slice0, int32_t batch, int32_t part_mask,
+                                           const float* reg_rows, int32_t n_reg, const vittf_rope_table* rope, uint16_t* q_out,
+                                           uint16_t* k_out, uint16_t* v_out, void* ws, size_t ws_bytes, void* stream) {
+  if (part_mask <= 0 || part_mask > 7) return VITTF_ERR_INVALID_ARG;
+  return vittf_vit_features(cfg, w, pos, view, slice0, batch, part_mask, reg_rows, n_reg, rope, nullptr, nullptr, q_out, k_out,
+                            v_out, nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int vittf_vit_qkv_features_reg(const vittf_vit_config* cfg, const vittf_vit_weights* w, const vittf_pos_embed* pos,

@@ -17,6 +17,18 @@ from .weights import (DINOV3_LN_EPS, arch_of, dinov3_canonical, fold_layer_scale
 _TORCH_DT = {_lib.BF16: torch.bfloat16, _lib.FP16: torch.float16}
 
 
+def resolve_layer(layer, depth):
+    """Index of the hooked block: 0-based, negatives count from the end, None = the last block.  ValueError when out of range."""
+    if layer is None:
+        return int(depth) - 1
+    idx = int(layer)
+    if idx < 0:
+        idx += int(depth)
+    if not 0 <= idx < int(depth):
+        raise ValueError(f'layer {layer} is out of range for a model of {depth} blocks (valid: {-int(depth)} .. {int(depth) - 1})')
+    return idx
+
+
 class _Attn:
     def __init__(self, heads):
         self.num_heads = heads
@@ -44,15 +56,20 @@ class HipViT:
     quantises q and k inside the qkv GEMM, before the rotation.
     fused_tail=False: ViT-S without the packed weight streams (the block tail and the activation-stationary qkv GEMM): the GEMM
     launches every other width uses; flags: _lib.CFG_* bits (vittf_vit_config.flags), the slower alternatives the tests also run.
+    layer: the hooked block (resolve_layer: 0-based, negatives from the end, default the last): q, k and v are the thirds of
+    ``blocks[layer].attn.qkv``, the token facet (part 3) is the model's final ``norm`` of the patch tokens behind ``blocks[layer]``
+    (``get_intermediate_layers(norm=True)``).  The engine is told a model of ``layer + 1`` blocks; the weight stacks stay whole.
     """
 
-    def __init__(self, state_dict, arch='vits8', dtype='fp16', device=None, attention='16bit', fused_tail=True, flags=0):
+    def __init__(self, state_dict, arch='vits8', dtype='fp16', device=None, attention='16bit', fused_tail=True, flags=0,
+                 layer=None):
         self.lib = _lib.require_device()
         self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
         dim, depth, heads, patch = arch_of(arch)
         if heads * 64 != dim:
             raise ValueError('HipViT supports head dim 64 only (all DINO ViTs)')
         self.embed_dim, self.depth, self.num_heads, self.patch_size = dim, depth, heads, patch
+        self.layer = resolve_layer(layer, depth)
         self.dtype_id = _lib.DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
         self.dtype_name = 'bf16' if self.dtype_id == _lib.BF16 else 'fp16'
         self.blocks = [_Block(heads) for _ in range(depth)]    # duck-typing of model.blocks[-1].attn.num_heads
@@ -66,7 +83,7 @@ class HipViT:
                 raise ValueError('attention=\'fp8\' is not available for DINOv3: q and k are quantised inside the qkv GEMM, before '
                                  'the rotary embedding could be applied')
             sd = dinov3_canonical(sd)
-        self.cfg = _lib.VitConfig(dim, depth, heads, patch, self.dtype_id, DINOV3_LN_EPS if self.rope else 1e-6,
+        self.cfg = _lib.VitConfig(dim, self.layer + 1, heads, patch, self.dtype_id, DINOV3_LN_EPS if self.rope else 1e-6,
                                   1 if attention == 'fp8' else 0, int(flags))
         self.num_register_tokens = register_tokens_of(arch, sd)
         self._pos_antialias = pos_embed_antialias_of(arch, sd)
@@ -97,6 +114,10 @@ class HipViT:
             ptrs['tail_packed'] = self._t['tail_packed'].data_ptr()
             ptrs['qkv_packed'] = self._t['qkv_packed'].data_ptr()
         self.weights = _lib.VitWeights(**ptrs)
+        # the model's final LayerNorm (fp32): only the token facet runs it, so only that facet needs it in the state dict
+        has_norm = 'norm.weight' in sd and 'norm.bias' in sd
+        self._norm_g = sd['norm.weight'].to(dev, torch.float32).contiguous() if has_norm else None
+        self._norm_b = sd['norm.bias'].to(dev, torch.float32).contiguous() if has_norm else None
         # [R][D] fp32 rows the embedding kernels copy behind CLS (no position embedding)
         self._reg = sd['register_tokens'].reshape(-1, dim).to(dev).contiguous() if self.num_register_tokens else None
         self._cls = sd['cls_token'].reshape(1, 1, dim)
@@ -155,30 +176,34 @@ class HipViT:
         return (view.out_rows // p) * (view.out_cols // p) + 1 + self.num_register_tokens
 
     def k_features(self, view, slice0, batch, out, part=1):
-        """Run slices [slice0, slice0+batch) of `view` (a _lib.SliceView) through the ViT and write the
-        hooked qkv third (`part`: 0 q, 1 k, 2 v) of the patch tokens as fp16 into `out`
-        (tensor of >= batch * f0*f1 * D halves)."""
+        """Run slices [slice0, slice0+batch) of `view` (a _lib.SliceView) through the ViT and write one facet of the patch
+        tokens as fp16 into `out` (tensor of >= batch * f0*f1 * D halves).  `part`: 0 q, 1 k, 2 v -- that third of the hooked
+        qkv tensor of block `self.layer` --, 3 t -- the final-norm patch tokens behind that block."""
         self.qkv_features(view, slice0, batch, {int(part): out})
 
     def qkv_features(self, view, slice0, batch, outs):
-        """One forward of slices [slice0, slice0+batch) for several thirds of the hooked qkv tensor: `outs` maps a part
-        (0 q, 1 k, 2 v) to its output tensor, each written as k_features(part) writes it (same bits)."""
+        """One forward of slices [slice0, slice0+batch) for several facets: `outs` maps a part (0 q, 1 k, 2 v, 3 t) to its
+        output tensor, each written as k_features(part) writes it (same bits)."""
         tokens = self.tokens_for(view)
         npatch = tokens - 1 - self.num_register_tokens
         pos, _, _ = self.pos_for(view.out_rows, view.out_cols)
         ws = self.workspace(batch, tokens)
-        ptrs = [None, None, None]
+        ptrs = [None, None, None, None]
         for part, out in outs.items():
+            if int(part) not in (0, 1, 2, 3):
+                raise ValueError(f'part must be 0 (q), 1 (k), 2 (v) or 3 (t), got {part!r}')
             assert out.dtype == torch.float16 and out.is_contiguous() and \
                 out.numel() >= batch * npatch * self.embed_dim
             ptrs[int(part)] = _lib.ptr(out)
         mask = sum(1 << int(part) for part in outs)
+        if mask & 8 and self._norm_g is None:
+            raise ValueError('the token facet needs the final LayerNorm: the state dict has no norm.weight / norm.bias')
         rope = self.rope_for(view.out_rows, view.out_cols)
-        rc = self.lib.vittf_vit_qkv_features_rope(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view),
-                                                  slice0, batch, mask, _lib.ptr(self._reg), self.num_register_tokens,
-                                                  C.byref(rope[0]) if rope else None, *ptrs, _lib.ptr(ws), ws.numel(),
-                                                  _lib.stream_ptr())
-        _lib.check(rc, 'vittf_vit_qkv_features_rope')
+        rc = self.lib.vittf_vit_features(C.byref(self.cfg), C.byref(self.weights), C.byref(pos), C.byref(view), slice0, batch,
+                                         mask, _lib.ptr(self._reg), self.num_register_tokens,
+                                         C.byref(rope[0]) if rope else None, _lib.ptr(self._norm_g), _lib.ptr(self._norm_b),
+                                         *ptrs, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, 'vittf_vit_features')
 
     def __call__(self, *_a, **_k):
         raise _lib.VittfError('HipViT is driven through compute_qkv / FeatureExtractor, not called on image tensors')

@@ -75,7 +75,7 @@ def wide_batch_limit(tokens, embed_dim):
     return max(1, min(by_hidden, by_kfeat))
 
 
-PARTS = {'q': 0, 'k': 1, 'v': 2}
+PARTS = {'q': 0, 'k': 1, 'v': 2, 't': 3}    # 't': the final-norm patch tokens (HipViT.k_features part 3)
 # VITTF_DIST_FORCE=1: run the slab exchange even when the process group has ONE rank (the collective then moves nothing, but
 # every call of the multi-rank path -- the in-place all_gather_into_tensor, its deferred wait -- executes on the backend)
 DIST_FORCE = __import__('os').environ.get('VITTF_DIST_FORCE', '0') == '1'
@@ -148,7 +148,8 @@ def _slice_tokens(model, f0, f1):
 
 
 def k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, part=1, out=None):
-    """Token-major fp16 features of slices [s0, s1) of one axis: tensor [s1-s0, f0*f1, D] on the device."""
+    """Token-major fp16 features (`part`: 0 q, 1 k, 2 v, 3 t) of slices [s0, s1) of one axis: tensor [s1-s0, f0*f1, D] on the
+    device."""
     _, _, _, _, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
     engine_batch = engine_batch_for(_slice_tokens(model, f0, f1), model.embed_dim, engine_batch,
                                     n_reg=int(getattr(model, 'num_register_tokens', 0)))
@@ -164,7 +165,7 @@ def k_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, part=1, out
 
 
 def qkv_slices(model, dvol, axis, im_sizes, s0, s1, engine_batch=None, parts=(0, 1, 2)):
-    """k_slices for several thirds of the hooked qkv tensor (`parts`: 0 q, 1 k, 2 v) from ONE engine forward per slice
+    """k_slices for several facets (`parts`: 0 q, 1 k, 2 v of the hooked qkv tensor, 3 t) from ONE engine forward per slice
     batch: a list of tensors [s1-s0, f0*f1, D], in the order of `parts`, each with the bits k_slices(part) gives."""
     _, _, _, _, f0, f1 = _axis_geometry(dvol.shape, im_sizes, axis, model.patch_size)
     engine_batch = engine_batch_for(_slice_tokens(model, f0, f1), model.embed_dim, engine_batch,
