@@ -469,6 +469,30 @@ int vittf_topk_voxels(const float* maps, int32_t nmaps, int64_t nvox, int32_t k,
  * with eps 1e-8) or mean_j |x_i - x_j|_2 (measure 1, torch.cdist); x fp32 [n][f], dist fp32 [n]. */
 int vittf_mean_pairwise_distance(const float* x, int32_t n, int32_t f, int32_t measure, float* dist, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PCA reduction of a feature volume (vit-tf_amd/pca.py, reduce_features.py, infer.py --pca): the first principal
+ * components of the dense features, as the DINOv2 / DINOv3 papers show them, as a colour volume or a compact volume the
+ * similarity entries above take unchanged.  feat: fp16 [f][nvox], the F-major file layout, 2-byte aligned; f a multiple of
+ * 32 in 32..1024; nvox >= 1, any value (rows that are not 16-byte aligned take a slower load path).
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_GRAM_RUN 2048   /* most voxels one fp32 accumulator of the Gram kernel covers before it is added into fp64 */
+#define VITTF_PCA_MAX_K 64    /* most components of one projection call */
+
+/* gram[i][j] = sum_v x_iv x_jv (fp64 [f][f], both triangles, exactly symmetric) and sums[i] = sum_v x_iv (fp64 [f]).
+ * fp16 MFMAs with fp32 accumulation (every product is exact) over runs of at most VITTF_GRAM_RUN voxels; the runs are summed
+ * in fp64 in a fixed order and there are no floating-point atomics: the same call gives the same bits.  The eigenproblem
+ * of the f x f covariance is host work (pca.py basis_from_gram).  gram, sums, ws: 8-byte aligned; ws: >=
+ * vittf_feature_gram_workspace_bytes(f, nvox) bytes (0 for an f or nvox the call refuses). */
+size_t vittf_feature_gram_workspace_bytes(int32_t f, int64_t nvox);
+int vittf_feature_gram(const uint16_t* feat, int32_t f, int64_t nvox, double* gram, double* sums, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/* out[c][v] = fp16(sum_f comp[c][f] x_fv - offset[c]): fp16 [k][nvox], F-major like the input, rounded once.  comp fp32
+ * [k][f], taken as fp16 hi + lo halves (to 2^-22 relative) with fp32 accumulation; offset fp32 [k] or NULL (zeros);
+ * 1 <= k <= VITTF_PCA_MAX_K.  The volume is read once. */
+int vittf_feature_project(const uint16_t* feat, int32_t f, int64_t nvox, const float* comp, const float* offset, int32_t k,
+                          uint16_t* out, void* stream);
+
 /* ---- label-volume helpers: sampler candidate masks and scores --------------------------- */
 /* dst = binary_erosion(set, generate_binary_structure(3, connectivity)) with scipy.ndimage's defaults (one iteration,
  * border_value 0): set = {src == class_id} (class_id 0..255) or {src != 0} (class_id < 0); uint8 volumes (n0, n1, n2),

@@ -16,6 +16,10 @@ Differences a caller can observe:
     projection, or ``token`` -- the model's final-norm patch tokens, the dense feature DINOv2 / DINOv3 publish
     (x_norm_patchtokens); ``--layer N`` hooks block N (0-based, negatives from the end) instead of the last one.  The file's
     dict key is the facet's letter (q, k, v, t); a non-default facet or layer is appended to the default file name
+  * ``--pca K`` saves the first K principal components of the feature volume instead of its F channels (vt.pca: Gram and
+    projection kernels on the GPU, the F x F eigenproblem on the host) and writes the basis beside the file
+    (``<file stem>_basis.npz``); ``--pca-basis FILE`` applies a saved basis instead of fitting one; ``_pca<K>`` is appended to
+    the default file name.  reduce_features.py does the same to an existing feature file
   * launched under torchrun, the slices of each axis are sharded over the ranks and reassembled with one
     RCCL all-gather per axis; rank 0 writes the file
 """
@@ -245,15 +249,29 @@ def handle_output_path(args):
             idx = vt.engine.resolve_layer(layer, depth)
             if idx != depth - 1:
                 stem += f'_L{idx}'
+        pca = getattr(args, 'pca', None)
+        if pca:
+            stem += f'_pca{pca}'
         args.cache_path = data_path.parent / f'{stem}{data_path.suffix}'
     cache_path = Path(args.cache_path)
     if cache_path.exists() and not args.overwrite:
         print(f'Cache file already exists: {cache_path}. Use --overwrite to overwrite.')
         sys.exit(1)
+    if getattr(args, 'pca', None) and not getattr(args, 'pca_basis', None):       # a fitted basis is written beside the file
+        basis_path = pca_basis_path(cache_path)
+        if basis_path.exists() and not args.overwrite:
+            print(f'Cache file already exists: {basis_path}. Use --overwrite to overwrite.')
+            sys.exit(1)
     if not os.access(os.path.dirname(str(cache_path)) or os.getcwd(), os.W_OK):
         print(f'Invalid argument for --cache-path (Cannot write to location): {args.cache_path}')
         sys.exit(1)
     return cache_path
+
+
+def pca_basis_path(cache_path):
+    """Where --pca writes the basis it fitted: ``<stem>_basis.npz`` beside the feature file."""
+    cache_path = Path(cache_path)
+    return cache_path.with_name(cache_path.stem + '_basis.npz')
 
 
 def save_features(qkv, cache_path):
@@ -305,6 +323,27 @@ def _agree_on_output_path(args, rank, world):
     return cache_path
 
 
+def _pca_arguments(args):
+    """--pca / --pca-basis: the loaded basis (or None); args.pca becomes the number of components saved.  Exits with 1 on a
+    K outside 1..VITTF_PCA_MAX_K, an unreadable basis file, or a K that contradicts the basis."""
+    basis = None
+    if args.pca_basis:
+        try:
+            basis = vt.pca.load_basis(args.pca_basis)
+        except (OSError, ValueError, KeyError) as e:
+            print(f'Invalid argument for --pca-basis: {e}')
+            sys.exit(1)
+        k = int(basis.components.shape[0])
+        if args.pca is not None and args.pca != k:
+            print(f'Invalid argument for --pca: {args.pca} components asked for, the basis {args.pca_basis} holds {k}')
+            sys.exit(1)
+        args.pca = k
+    if args.pca is not None and not 1 <= args.pca <= vt._lib.PCA_MAX_K:
+        print(f'Invalid argument for --pca: {args.pca} is outside 1..{vt._lib.PCA_MAX_K}')
+        sys.exit(1)
+    return basis
+
+
 def main(argv=None):
     from argparse import ArgumentParser
     dino_archs = ['vits16', 'vits8', 'vitb16', 'vitb8']
@@ -335,6 +374,9 @@ def main(argv=None):
                         help='what to save: key / query / value = that third of the hooked qkv projection (key: the reference), '
                         'token = the final-norm patch tokens behind the hooked block (x_norm_patchtokens of DINOv2 / DINOv3)')
     parser.add_argument('--layer', type=int, default=-1, help='hooked block, 0-based; negatives count from the end (default -1: the last block)')
+    parser.add_argument('--pca', type=int, default=None, metavar='K', help=f'save the first K principal components (1..{vt._lib.PCA_MAX_K}) of the feature '
+                        'volume instead of its F channels; the basis goes beside the file (<stem>_basis.npz)')
+    parser.add_argument('--pca-basis', type=str, default=None, metavar='FILE', help='apply this saved basis (.npz of --pca / reduce_features.py) instead of fitting one')
     args = parser.parse_args(argv)
 
     if args.cpu:
@@ -349,6 +391,7 @@ def main(argv=None):
             print(f'Invalid argument for --layer: {e}')
             sys.exit(1)
     _MODEL_OPTS['layer'] = args.layer
+    pca_basis = _pca_arguments(args)
     rank, world = _init_distributed()
     cache_path = _agree_on_output_path(args, rank, world)
 
@@ -356,11 +399,22 @@ def main(argv=None):
     im_sz, feat_out_sz = vt.sizing(tuple(vol.shape), args.feature_output_size, patch_size)
     print(f'Input image size: {im_sz}')
     model = dino_model_fn(dino_model)
+    if pca_basis is not None and int(pca_basis.components.shape[1]) != model.embed_dim:      # (every rank decides the same)
+        print(f'Invalid argument for --pca-basis: fitted on F = {int(pca_basis.components.shape[1])} features, {args.model} has F = {model.embed_dim}')
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        sys.exit(1)
     torch.cuda.synchronize()
     t0 = time.time()
     eb = vt.extract.AtLeast(args.batch_size) if args.batch_size > 1 else None   # a lower bound (extract.engine_batch_for)
     key = FACETS[args.facet]
     feats = vt.feature_volume(vol, model, args.feature_output_size, args.slice_along, eb, part=vt.extract.PARTS[key])
+    basis = None
+    if args.pca and rank == 0:             # rank 0 reduces the assembled volume; the F-channel volume is not saved
+        if pca_basis is None:
+            feats, basis = vt.pca.reduce_features(feats, args.pca)
+        else:
+            feats = vt.pca.project(feats, pca_basis)
     if args.slice_along == 'all':
         qkv = defaultdict(float)           # the reference saves a defaultdict in 'all' mode (:328)
         qkv[key] = feats.cpu()
@@ -370,6 +424,9 @@ def main(argv=None):
         print(key, ':', qkv[key].shape)
         print(f'Computed qkv along {args.slice_along} in {time.time() - t0}s, saving now to: {cache_path}')
         save_features(qkv, cache_path)
+        if basis is not None:
+            vt.pca.save_basis(basis, pca_basis_path(cache_path))
+            print(f'PCA basis of {args.pca} components saved to: {pca_basis_path(cache_path)}')
     if world > 1 or torch.distributed.is_initialized():
         if rank == 0:
             print('slab exchanges:', ', '.join(f'{n} over {b}' for b, n in sorted(vt.extract.EXCHANGES.items())) or 'none')

@@ -112,6 +112,9 @@ SIGNATURES = {
                                          _vp, _vp, _sz, _vp]),
     'vittf_similarity_maps_f32': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _P(_i32), _i32, _i32, C.c_float, _vp, _vp,
                                             _vp, _sz, _vp]),
+    'vittf_feature_gram_workspace_bytes': (_sz, [_i32, _i64]),
+    'vittf_feature_gram': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_feature_project': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
     'vittf_topk_voxels': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
     'vittf_mean_pairwise_distance': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     'vittf_erode_mask': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -155,6 +158,8 @@ KERNEL_CLASSES = ('patch_embed', 'layernorm', 'gemm', 'attention', 'mlp', 'gemm_
 ABI_VERSION = 6
 MAX_REGISTER_TOKENS = 8   # VITTF_MAX_REGISTER_TOKENS
 QUERY_MAX_A = 64          # VITTF_QUERY_MAX_A: annotations of a vittf_similarity_query call
+GRAM_RUN = 2048           # VITTF_GRAM_RUN: voxels per fp32 accumulation run of vittf_feature_gram
+PCA_MAX_K = 64            # VITTF_PCA_MAX_K: components of one vittf_feature_project call
 
 
 def profiler_enable(on=True, classes=None):
