@@ -493,6 +493,30 @@ int vittf_feature_gram(const uint16_t* feat, int32_t f, int64_t nvox, double* gr
 int vittf_feature_project(const uint16_t* feat, int32_t f, int64_t nvox, const float* comp, const float* offset, int32_t k,
                           uint16_t* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-means clustering of a feature volume (vit-tf_amd/kmeans.py, cluster_features.py): the two passes over the volume of
+ * one Lloyd iteration.  feat, f, nvox: as for the PCA entries above (fp16 [f][nvox], 2-byte aligned, f a multiple of 32 in
+ * 32..1024, nvox >= 1; rows that are not 16-byte aligned take a slower load path).  2 <= c <= VITTF_KMEANS_MAX_C.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_KMEANS_MAX_C 64   /* most clusters of one call */
+
+/* labels[v] = argmax_c (sum_f cent[c][f] x_fv - half_sq[c]); the lowest index wins among equal fp32 scores.  With half_sq[c]
+ * = 0.5 |m_c|^2 that is the nearest centroid in squared Euclidean distance.  cent fp32 [c][f], taken as fp16 hi + lo halves
+ * (to 2^-22 relative) with fp32 accumulation; half_sq fp32 [c] or NULL (zeros); labels uint8 [nvox]; best fp32 [nvox] or NULL:
+ * the winning score.  The volume is read once. */
+int vittf_kmeans_assign(const uint16_t* feat, int32_t f, int64_t nvox, const float* cent, const float* half_sq, int32_t c,
+                        uint8_t* labels, float* best, void* stream);
+
+/* sums[k][i] = sum over {v: labels[v] == k} of x_iv (fp64 [c][f]) and counts[k] = the number of such voxels (int64 [c]).  A
+ * voxel whose label is >= c contributes nowhere (255 masks a voxel out).  fp16 MFMAs against a 0/1 operand (every product
+ * is exact) with fp32 accumulation over runs of at most VITTF_GRAM_RUN voxels; the runs are summed in fp64 in a fixed order
+ * and there are no floating-point atomics: the same call gives the same bits.  The volume is cut into at most 128 spans of
+ * whole runs; ws: >= vittf_kmeans_sums_workspace_bytes(f, nvox, c) = spans x ((f / 32) ceil(c / 32) x 1024 + 64) x 8 bytes
+ * (at most 67 MB; 0 for a shape the call refuses).  sums, counts, ws: 8-byte aligned. */
+size_t vittf_kmeans_sums_workspace_bytes(int32_t f, int64_t nvox, int32_t c);
+int vittf_kmeans_sums(const uint16_t* feat, int32_t f, int64_t nvox, const uint8_t* labels, int32_t c, double* sums,
+                      int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- label-volume helpers: sampler candidate masks and scores --------------------------- */
 /* dst = binary_erosion(set, generate_binary_structure(3, connectivity)) with scipy.ndimage's defaults (one iteration,
  * border_value 0): set = {src == class_id} (class_id 0..255) or {src != 0} (class_id < 0); uint8 volumes (n0, n1, n2),

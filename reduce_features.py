@@ -53,7 +53,7 @@ def load_features(path):
     return letter, feats
 
 
-def _writable(path, flag, overwrite):
+def writable_path(path, flag, overwrite):
     """infer.handle_output_path's refusals for one output file."""
     path = Path(path)
     if path.exists() and not overwrite:
@@ -107,9 +107,9 @@ def main(argv=None):
     if f % 32 or not 32 <= f <= 1024:
         print(f'Invalid argument for --features: F = {f} is not a multiple of 32 in 32..1024')
         sys.exit(1)
-    out_path = _writable(args.output or src.with_name(f'{src.stem}_pca{k}{src.suffix}'), '--output', args.overwrite)
-    basis_path = None if basis is not None else _writable(out_path.with_name(out_path.stem + '_basis.npz'), '--output', args.overwrite)
-    rgb_path = _writable(src.with_name(f'{src.stem}_pca_rgb.npy'), '--rgb', args.overwrite) if args.rgb else None
+    out_path = writable_path(args.output or src.with_name(f'{src.stem}_pca{k}{src.suffix}'), '--output', args.overwrite)
+    basis_path = None if basis is not None else writable_path(out_path.with_name(out_path.stem + '_basis.npz'), '--output', args.overwrite)
+    rgb_path = writable_path(src.with_name(f'{src.stem}_pca_rgb.npy'), '--rgb', args.overwrite) if args.rgb else None
 
     if basis is None:
         reduced, basis = vt.pca.reduce_features(feats, k, center=not args.no_center)

@@ -115,6 +115,9 @@ SIGNATURES = {
     'vittf_feature_gram_workspace_bytes': (_sz, [_i32, _i64]),
     'vittf_feature_gram': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
     'vittf_feature_project': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
+    'vittf_kmeans_assign': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    'vittf_kmeans_sums_workspace_bytes': (_sz, [_i32, _i64, _i32]),
+    'vittf_kmeans_sums': (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     'vittf_topk_voxels': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
     'vittf_mean_pairwise_distance': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     'vittf_erode_mask': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -160,6 +163,8 @@ MAX_REGISTER_TOKENS = 8   # VITTF_MAX_REGISTER_TOKENS
 QUERY_MAX_A = 64          # VITTF_QUERY_MAX_A: annotations of a vittf_similarity_query call
 GRAM_RUN = 2048           # VITTF_GRAM_RUN: voxels per fp32 accumulation run of vittf_feature_gram
 PCA_MAX_K = 64            # VITTF_PCA_MAX_K: components of one vittf_feature_project call
+KMEANS_MAX_C = 64         # VITTF_KMEANS_MAX_C: clusters of one vittf_kmeans_assign / vittf_kmeans_sums call
+KMEANS_SPANS = 128        # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
 def profiler_enable(on=True, classes=None):

@@ -18,8 +18,10 @@
 // is the operand that needs transposed fragments: a workgroup stages [32 feature rows][256 voxels] parts in LDS and every
 // wave picks the 8 features of its 32 voxels up with ds_read_b64_tr_b16 (sim_mfma.hip's pickup).  The components are split
 // into fp16 hi + lo halves (comp = hi + lo to 2^-22, sim_mfma_prep's arithmetic) by the workgroup itself, part by part,
-// k padded with zero rows to 32 or 64; fp32 accumulation, one rounding to fp16; the volume is read once.
+// k padded with zero rows to 32 or 64; fp32 accumulation, one rounding to fp16; the volume is read once.  That loop is
+// project_scores in feat_rows.h, which the k-means assignment (kmeans.hip) shares.
 #include "vittf_common.h"
+#include "feat_rows.h"
 
 namespace {
 
@@ -27,7 +29,7 @@ namespace {
 constexpr int GR_THREADS = 512, GR_WAVES = 8;
 constexpr int GR_STEP = 32;                         // voxels per staged step: two MFMA k-steps
 constexpr int GR_ROW = 2 * GR_STEP + 16;            // LDS bytes per staged row (16 bytes of padding: odd number of 16-byte slots)
-constexpr int GR_MAXF = 1024;
+constexpr int GR_MAXF = FEAT_MAXF;
 constexpr int GR_NARROW = 384;                      // f up to here: 10 accumulator tiles per wave, 3 staged chunks per thread
 constexpr int GR_SLOTS_NARROW = 10, GR_SLOTS_WIDE = 6;   // accumulator tiles per wave; x GR_WAVES = tiles per workgroup
 constexpr int GR_UNITS = 128;                       // most voxel spans (over all tile groups): bounds the workspace
@@ -57,20 +59,6 @@ __device__ __forceinline__ void gram_pair(int p, int nb, int& bi, int& bj) {
   bi = 0;
   while (rem >= nb - bi) { rem -= nb - bi; ++bi; }
   bj = bi + rem;
-}
-
-template <bool ALIGNED>
-__device__ __forceinline__ uint4 gram_load8(const unsigned short* __restrict__ row, int64_t v, int64_t nvox) {
-  uint4 c = make_uint4(0u, 0u, 0u, 0u);
-  if constexpr (ALIGNED) {
-    if (v < nvox) c = *reinterpret_cast<const uint4*>(row + v);       // nvox % 8 == 0: the chunk is inside the row
-  } else {
-    unsigned e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = v + j < nvox ? (unsigned)row[v + j] : 0u;
-    c = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
-  }
-  return c;
 }
 
 __device__ __forceinline__ float sum8_f16(uint4 c) {
@@ -222,90 +210,18 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ projection
-constexpr int PJ_THREADS = 512;
-constexpr int PJ_VOX = 256;                  // voxels per workgroup: 32 per wave
-constexpr int PJ_ROWS = 32;                  // feature rows per staged part: two MFMA k-steps
-constexpr int PJ_VROW = 2 * PJ_VOX + 64;     // LDS bytes per staged feature row: the four rows of a transposing read on four bank quarters
-constexpr int PJ_CROW = 2 * PJ_ROWS + 16;    // LDS bytes per component row of a part (hi or lo)
-
 // RB = 32-row blocks of the padded components (k <= 32 RB)
 template <bool ALIGNED, int RB>
 __global__ __launch_bounds__(PJ_THREADS) void project_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
                                                              const float* __restrict__ comp, const float* __restrict__ offset,
                                                              int k, unsigned short* __restrict__ out) {
-  constexpr int KP = 32 * RB;
   __shared__ __attribute__((aligned(16))) char vbuf[PJ_ROWS * PJ_VROW];
-  __shared__ __attribute__((aligned(16))) char cbuf[2 * KP * PJ_CROW];       // hi rows, then lo rows
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  __shared__ __attribute__((aligned(16))) char cbuf[2 * 32 * RB * PJ_CROW];  // hi rows, then lo rows
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int h = lane >> 5, l31 = lane & 31;
   const int64_t v0 = (int64_t)blockIdx.x * PJ_VOX;
-  const int parts = f / PJ_ROWS;
-
-  // staging of a part: the volume's [32][256] as 1024 chunks of 8 voxels, two per thread; the components' [KP][32] as
-  // KP x 8 groups of four, one per thread
-  uint4 pre[2];
-  float cpre[4];
-  const int crow = tid >> 3, cq = tid & 7;
-  auto prefetch = [&](int part) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = tid + PJ_THREADS * j;
-      pre[j] = gram_load8<ALIGNED>(feat + (int64_t)(part * PJ_ROWS + (i >> 5)) * nvox, v0 + 8 * (i & 31), nvox);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) cpre[j] = (crow < k) ? comp[(int64_t)crow * f + part * PJ_ROWS + 4 * cq + j] : 0.f;
-  };
-  // transposing read (sim_mfma.hip): 16-lane group g covers voxels 16 (g & 1) .. + 15 of the wave's 32 and feature group
-  // g >> 1; lane 4 q + p of the group addresses row q, voxels 4 p .. 4 p + 3; it receives 4 features of ITS voxel
-  const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-  const int tr_off = (8 * (grp >> 1) + qq) * PJ_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
-  const int a_off = l31 * PJ_CROW + 16 * h;
-
   f32x16_t acc[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-
-  prefetch(0);
-  for (int part = 0; part < parts; ++part) {
-    __syncthreads();                                   // the previous part's fragments have been read
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int i = tid + PJ_THREADS * j;
-      *reinterpret_cast<uint4*>(vbuf + (i >> 5) * PJ_VROW + 16 * (i & 31)) = pre[j];
-    }
-    if (crow < KP) {
-      unsigned short hi[4], lo[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        hi[j] = f32_to_f16bits(cpre[j]);
-        lo[j] = f32_to_f16bits(cpre[j] - f16bits_to_f32(hi[j]));
-      }
-      char* dst = cbuf + crow * PJ_CROW + 8 * cq;
-      *reinterpret_cast<uint2*>(dst) = make_uint2((unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16));
-      *reinterpret_cast<uint2*>(dst + KP * PJ_CROW) = make_uint2((unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16));
-    }
-    __syncthreads();
-    if (part + 1 < parts) prefetch(part + 1);
-#pragma unroll
-    for (int s = 0; s < PJ_ROWS / 16; ++s) {
-      const char* buf = vbuf + tr_off + (16 * s) * PJ_VROW;
-      const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
-      const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * PJ_VROW));
-      s16x8_t x;
-      x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
-#pragma unroll
-      for (int b = 0; b < RB; ++b) {
-        const char* cb = cbuf + (32 * b) * PJ_CROW + a_off + 32 * s;
-        const s16x8_t ch = *reinterpret_cast<const s16x8_t*>(cb);
-        const s16x8_t cl = *reinterpret_cast<const s16x8_t*>(cb + KP * PJ_CROW);
-        acc[b] = mfma32<VITTF_FP16>(ch, x, acc[b]);
-        acc[b] = mfma32<VITTF_FP16>(cl, x, acc[b]);
-      }
-    }
-  }
+  project_scores<ALIGNED, RB>(feat, f, nvox, comp, k, v0, vbuf, cbuf, acc);
   const int64_t v = v0 + wave * 32 + l31;
   if (v < nvox) {
 #pragma unroll
@@ -317,9 +233,6 @@ __global__ __launch_bounds__(PJ_THREADS) void project_kernel(const unsigned shor
       }
   }
 }
-
-static bool rows_aligned(const void* feat, int64_t nvox) { return nvox % 8 == 0 && ((uintptr_t)feat & 15) == 0; }
-static bool gram_f_ok(int32_t f) { return f >= 32 && f <= GR_MAXF && f % 32 == 0; }
 
 }  // namespace
 
