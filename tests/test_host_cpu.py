@@ -296,6 +296,30 @@ def test_block_tail_kernel_register_contract(tmp_path):
         assert 'flat_load' not in asm
 
 
+def test_span_kernel_register_contract(tmp_path):
+    """gram_kernel (csrc/pca.hip) and sums_kernel (csrc/kmeans.hip) hold up to 160 accumulator registers per lane and flush them
+    through flush_tile (csrc/span_rows.h), whose opaque lane offset keeps the compiler from forming every tile's store addresses
+    ahead of the step loop and spilling them.  For every instantiation: no scratch, no vector-register spill, and no fewer waves
+    per SIMD than these kernels had with a copy of that loop each.  Read from the resource-usage remarks alone."""
+    import re
+    import shutil
+    if not shutil.which('/opt/rocm/bin/hipcc'):
+        pytest.skip('no hipcc')
+    # template arguments behind the alignment flag -> waves per SIMD
+    floors = {'gram_kernel': {'Li10ELi3E': 2, 'Li6ELi8E': 2},
+              'sums_kernel': {'Li2ELi3ELi1E': 4, 'Li2ELi3ELi2E': 3, 'Li4ELi8ELi1E': 2, 'Li4ELi8ELi2E': 2}}
+    for src, kern in (('pca.hip', 'gram_kernel'), ('kmeans.hip', 'sums_kernel')):
+        r = _kernel_asm(src, tmp_path)
+        assert r.returncode == 0, r.stdout + r.stderr
+        usage = [l for l in r.stdout.splitlines() if re.search(r'\d+%sI' % kern, l) and 'ScratchSize' in l]
+        assert len(usage) == 2 * len(floors[kern]), r.stdout                     # aligned and unaligned rows
+        for l in usage:
+            floor = [v for k, v in floors[kern].items() if re.search(r'%sILb[01]E%sE' % (kern, k), l)]
+            assert len(floor) == 1, l
+            assert 'ScratchSize [bytes/lane]: 0 ' in l and ' VGPRs Spill: 0 ' in l, l
+            assert int(re.search(r'Occupancy \[waves/SIMD\]: (\d+)', l).group(1)) >= floor[0], l
+
+
 def test_window_goldens_cover_the_fullsize_tests():
     """tests/golden/windows512.npz (made by tests/golden/make_window_goldens.py from the CPU oracle) holds every pooled window the
     full-size GPU tests compare with: fp16, every 4th feature row / column of a (D, 64, 64) window, finite, not constant."""

@@ -1,5 +1,5 @@
 // Row access to an F-major fp16 feature volume [f][nvox] and the score loop over it, shared by the kernels that walk one
-// (pca.hip, kmeans.hip).
+// (pca.hip, kmeans.hip; the reduction along the voxels that the Gram and the cluster sums share is span_rows.h).
 #pragma once
 #include "vittf_common.h"
 
@@ -7,7 +7,7 @@ namespace {
 
 // 8 consecutive voxels v .. v + 7 of a row as one 16-byte chunk; voxels past the end are zeros
 template <bool ALIGNED>
-__device__ __forceinline__ uint4 gram_load8(const unsigned short* __restrict__ row, int64_t v, int64_t nvox) {
+__device__ __forceinline__ uint4 feat_load8(const unsigned short* __restrict__ row, int64_t v, int64_t nvox) {
   uint4 c = make_uint4(0u, 0u, 0u, 0u);
   if constexpr (ALIGNED) {
     if (v < nvox) c = *reinterpret_cast<const uint4*>(row + v);       // nvox % 8 == 0: the chunk is inside the row
@@ -22,7 +22,7 @@ __device__ __forceinline__ uint4 gram_load8(const unsigned short* __restrict__ r
 
 constexpr int FEAT_MAXF = 1024;
 static bool rows_aligned(const void* feat, int64_t nvox) { return nvox % 8 == 0 && ((uintptr_t)feat & 15) == 0; }
-static bool gram_f_ok(int32_t f) { return f >= 32 && f <= FEAT_MAXF && f % 32 == 0; }
+static bool feat_f_ok(int32_t f) { return f >= 32 && f <= FEAT_MAXF && f % 32 == 0; }
 
 // ---- scores of the rows of a small fp32 matrix against 256 voxels: the main loop of the projection and of the k-means
 // assignment.  acc[b][r] = sum_f mat[32 b + acc_row(r, h)][f] x[f][v] for voxel v = v0 + 32 wave + lane % 32 (fp32, an
@@ -57,7 +57,7 @@ __device__ __forceinline__ void project_scores(const unsigned short* __restrict_
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int i = tid + PJ_THREADS * j;
-      pre[j] = gram_load8<ALIGNED>(feat + (int64_t)(part * PJ_ROWS + (i >> 5)) * nvox, v0 + 8 * (i & 31), nvox);
+      pre[j] = feat_load8<ALIGNED>(feat + (int64_t)(part * PJ_ROWS + (i >> 5)) * nvox, v0 + 8 * (i & 31), nvox);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) cpre[j] = (crow < k) ? mat[(int64_t)crow * f + part * PJ_ROWS + 4 * cq + j] : 0.f;

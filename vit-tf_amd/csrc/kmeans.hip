@@ -11,22 +11,18 @@
 // among equal ones -- so the lowest index wins among equal fp32 scores, across lane halves and across the two row blocks.
 // The 256 one-byte labels of a workgroup are collected in LDS and stored four to a lane.
 //
-// vittf_kmeans_sums: sums[c][f] = sum over {v: labels[v] == c} of x_fv (fp64) = X onehot(labels)^T, and the cluster sizes.
-// The reduction runs along the voxels like the Gram's: a lane's 8 consecutive voxels of a feature row ARE the A fragment of
-// v_mfma_f32_32x32x16_f16 (gram_kernel's padded LDS staging, one 32-voxel step ahead through registers), the B fragment is
-// 0.0 / 1.0 fp16 built in registers from the step's 8 label bytes (label == the lane's cluster column), so every product is
-// exact.  Accumulator tiles: (f / 32) x ceil(c / 32), row block b on wave b % 8.  As in the Gram an fp32 accumulator covers
-// at most VITTF_GRAM_RUN voxels, then it is added into the workgroup's private fp64 partial in the workspace (the first run
-// writes, later runs read-add-write); a second kernel adds the partials in span order.  No floating-point atomics: the same
-// call gives the same bits.  The counts are integers: an LDS histogram per workgroup (integer LDS atomics, order-independent),
-// one int64 partial per span, added by the second kernel.
+// vittf_kmeans_sums: sums[c][f] = sum over {v: labels[v] == c} of x_fv (fp64) = X onehot(labels)^T, and the cluster sizes,
+// by the span reduction of span_rows.h: the A fragment is a staged feature row, the B fragment is 0.0 / 1.0 fp16 built in
+// registers from the step's 8 label bytes (label == the lane's cluster column), so every product is exact.  Accumulator
+// tiles: (f / 32) x ceil(c / 32), row block b on wave b % 8.  The counts are integers: an LDS histogram per workgroup
+// (integer LDS atomics, order-independent), one int64 partial per span, added by the second kernel.
 //   * spans: the volume is cut into at most KS_SPANS = 128 spans of whole runs (one workgroup each; a volume of more than
 //     128 runs gives a workgroup several runs); workspace = spans x ((f / 32) ceil(c / 32) x 1024 + 64) x 8 bytes,
 //     at most 128 x 65600 x 8 = 67 MB (f = 1024, c > 32), 25 MB at f = 384, c > 32;
 //   * a label >= c (255 = masked out) matches no column that is kept and is not counted; voxels past the end read as label
 //     255 and zero features.
 #include "vittf_common.h"
-#include "feat_rows.h"
+#include "span_rows.h"
 
 namespace {
 
@@ -81,50 +77,39 @@ __global__ __launch_bounds__(PJ_THREADS) void assign_kernel(const unsigned short
 }
 
 // ------------------------------------------------------------------------------------------------ cluster sums
-constexpr int KS_THREADS = 512, KS_WAVES = 8;
-constexpr int KS_STEP = 32;                         // voxels per staged step: two MFMA k-steps
-constexpr int KS_ROW = 2 * KS_STEP + 16;            // LDS bytes per staged row (gram_kernel's padding)
-constexpr int KS_NARROW = 384;                      // f up to here: 2 row blocks per wave, 3 staged chunks per thread
-constexpr int KS_RBW_NARROW = KS_NARROW / 32 / KS_WAVES + 1, KS_RBW_WIDE = FEAT_MAXF / 32 / KS_WAVES;      // row blocks per wave
-constexpr int KS_PRE_NARROW = KS_NARROW * (KS_STEP / 8) / KS_THREADS, KS_PRE_WIDE = FEAT_MAXF * (KS_STEP / 8) / KS_THREADS;
+constexpr int KS_RBW_NARROW = SPAN_NARROW / 32 / SPAN_WAVES + 1, KS_RBW_WIDE = FEAT_MAXF / 32 / SPAN_WAVES;      // row blocks per wave
 constexpr int KS_SPANS = 128;                       // most voxel spans: bounds the workspace
-static_assert(VITTF_GRAM_RUN % KS_STEP == 0 && VITTF_GRAM_RUN <= 4096, "an fp32 accumulator covers whole steps");
-static_assert(KS_RBW_NARROW * KS_WAVES * 32 >= KS_NARROW && KS_RBW_WIDE * KS_WAVES * 32 >= FEAT_MAXF, "every row block has a wave");
-static_assert(KS_THREADS % (KS_STEP / 8) == 0, "a thread's chunk column is the same for all its rows");
+static_assert(KS_RBW_NARROW * SPAN_WAVES * 32 >= SPAN_NARROW && KS_RBW_WIDE * SPAN_WAVES * 32 >= FEAT_MAXF, "every row block has a wave");
 
-struct SumsPlan { int nb, cbn, tiles, units; int64_t runs_per_unit; };
+struct SumsPlan { int nb, cbn, tiles; SpanPlan span; };
 
 static SumsPlan sums_plan(int f, int64_t nvox, int c) {
   SumsPlan p;
   p.nb = f / 32;
   p.cbn = (c + 31) / 32;
   p.tiles = p.nb * p.cbn;
-  const int64_t runs = (nvox + VITTF_GRAM_RUN - 1) / VITTF_GRAM_RUN;
-  p.runs_per_unit = (runs + KS_SPANS - 1) / KS_SPANS;
-  p.units = (int)((runs + p.runs_per_unit - 1) / p.runs_per_unit);
+  p.span = span_plan(nvox, KS_SPANS);
   return p;
 }
 
-// grid: units.  part: fp64 [units][tiles][1024] (tile = row block x CB + column block, in accumulator order: register r of
-// lane l at 16 l + r), pcounts: int64 [units][64].
+// grid: units.  part: fp64 [units][tiles][1024] (tile = row block x CB + column block, in accumulator order),
+// pcounts: int64 [units][64].
 // RBW: row blocks per wave, PRE: 16-byte chunks a thread stages per step, CB: 32-cluster column blocks
 template <bool ALIGNED, int RBW, int PRE, int CB>
-__global__ __launch_bounds__(KS_THREADS) void sums_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
-                                                          const unsigned char* __restrict__ labels, int c, int nb,
-                                                          int64_t runs_per_unit, double* __restrict__ part,
-                                                          unsigned long long* __restrict__ pcounts) {
-  __shared__ __attribute__((aligned(16))) char slab[PRE * KS_THREADS / (KS_STEP / 8) * KS_ROW];   // 30 KB (f <= 384) or 80 KB
-  __shared__ __attribute__((aligned(8))) unsigned char lab[KS_STEP];
+__global__ __launch_bounds__(SPAN_THREADS) void sums_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
+                                                            const unsigned char* __restrict__ labels, int c, int nb,
+                                                            int64_t runs_per_unit, double* __restrict__ part,
+                                                            unsigned long long* __restrict__ pcounts) {
+  __shared__ __attribute__((aligned(16))) char slab[span_slab_bytes(PRE)];   // 30 KB (f <= 384) or 80 KB
+  __shared__ __attribute__((aligned(8))) unsigned char lab[SPAN_STEP];
   __shared__ unsigned long long hist[VITTF_KMEANS_MAX_C];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
   const int unit = blockIdx.x;
-  const int64_t vbeg = (int64_t)unit * runs_per_unit * VITTF_GRAM_RUN;
-  const int64_t vend = vbeg + runs_per_unit * VITTF_GRAM_RUN < nvox ? vbeg + runs_per_unit * VITTF_GRAM_RUN : nvox;
-  const int64_t nsteps = (vend - vbeg + KS_STEP - 1) / KS_STEP;
+  const Span span(unit, runs_per_unit, nvox);
   // the wave's row blocks: wave, wave + 8, ...
-  const int nrb = nb > wave ? (nb - wave + KS_WAVES - 1) / KS_WAVES : 0;
+  const int nrb = nb > wave ? (nb - wave + SPAN_WAVES - 1) / SPAN_WAVES : 0;
 
   f32x16_t acc[RBW][CB];
 #pragma unroll
@@ -135,39 +120,28 @@ __global__ __launch_bounds__(KS_THREADS) void sums_kernel(const unsigned short* 
       for (int r = 0; r < 16; ++r) acc[t][cb][r] = 0.f;
   if (tid < VITTF_KMEANS_MAX_C) hist[tid] = 0ull;     // wave 0, which alone adds to it
 
-  // staging: 16-byte chunk (i & 3) of row (i >> 2), i = tid + KS_THREADS k; the step's 32 labels, one per thread of wave 0
-  const int nchunks = f * (KS_STEP / 8);
-  const int my_chunk = tid & (KS_STEP / 8 - 1);
-  uint4 pre[PRE];
+  // beside the rows the step's 32 labels are staged, one per thread of wave 0
+  RowStager<ALIGNED, PRE> rows(feat, f, nvox, span.vbeg);
   unsigned plab = 255u;
   auto prefetch = [&](int64_t step) {
-    const int64_t v = vbeg + step * KS_STEP + 8 * my_chunk;
-#pragma unroll
-    for (int k = 0; k < PRE; ++k) {
-      const int i = tid + KS_THREADS * k;
-      if (i < nchunks) pre[k] = gram_load8<ALIGNED>(feat + (int64_t)(i >> 2) * nvox, v, nvox);
-    }
-    if (tid < KS_STEP) {
-      const int64_t vl = vbeg + step * KS_STEP + tid;
+    rows.prefetch(step);
+    if (tid < SPAN_STEP) {
+      const int64_t vl = span.vbeg + step * SPAN_STEP + tid;
       plab = vl < nvox ? (unsigned)labels[vl] : 255u;
     }
   };
-  const int frag_off = l31 * KS_ROW + h * 16;
+  const int frag_off = span_frag_off(lane);
   bool first = true;
   prefetch(0);
-  for (int64_t step = 0; step < nsteps; ++step) {
+  for (int64_t step = 0; step < span.nsteps; ++step) {
     __syncthreads();                                  // the previous step's fragments have been read
-#pragma unroll
-    for (int k = 0; k < PRE; ++k) {
-      const int i = tid + KS_THREADS * k;
-      if (i < nchunks) *reinterpret_cast<uint4*>(slab + (i >> 2) * KS_ROW + 16 * my_chunk) = pre[k];
-    }
-    if (tid < KS_STEP) {
+    rows.commit(slab);
+    if (tid < SPAN_STEP) {
       lab[tid] = (unsigned char)plab;
       if (plab < (unsigned)c) atomicAdd(&hist[plab], 1ull);
     }
     __syncthreads();
-    if (step + 1 < nsteps) prefetch(step + 1);
+    if (step + 1 < span.nsteps) prefetch(step + 1);
     // B fragments: element j of k-step s is 1.0 where voxel 16 s + 8 h + j carries the lane's cluster 32 cb + l31
     s16x8_t bf[2][CB];
 #pragma unroll
@@ -184,7 +158,7 @@ __global__ __launch_bounds__(KS_THREADS) void sums_kernel(const unsigned short* 
 #pragma unroll
     for (int t = 0; t < RBW; ++t) {
       if (t < nrb) {                                  // (wave-uniform)
-        const char* ab = slab + (wave + KS_WAVES * t) * 32 * KS_ROW + frag_off;
+        const char* ab = slab + (wave + SPAN_WAVES * t) * 32 * SPAN_ROW + frag_off;
         const s16x8_t a0 = *reinterpret_cast<const s16x8_t*>(ab);
         const s16x8_t a1 = *reinterpret_cast<const s16x8_t*>(ab + 32);
 #pragma unroll
@@ -194,29 +168,12 @@ __global__ __launch_bounds__(KS_THREADS) void sums_kernel(const unsigned short* 
         }
       }
     }
-    // the end of a run of VITTF_GRAM_RUN voxels (or of the span): fp32 -> the workgroup's fp64 partial
-    if ((step + 1) % (VITTF_GRAM_RUN / KS_STEP) == 0 || step + 1 == nsteps) {
+    if (span.run_ends(step)) {
 #pragma unroll
-      for (int t = 0; t < RBW; ++t) {
+      for (int t = 0; t < RBW; ++t)
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) {
-          if (t < nrb) {
-            unsigned loff = 16 * lane;                      // 128 bytes per lane
-            asm volatile("" : "+v"(loff));                  // (gram_kernel's: keeps the store addresses from being formed ahead of the loop)
-            double* dst = part + ((int64_t)unit * nb * CB + (wave + KS_WAVES * t) * CB + cb) * 1024 + loff;
-            if (first) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) dst[r] = (double)acc[t][cb][r];
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) dst[r] += (double)acc[t][cb][r];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][cb][r] = 0.f;
-          }
-          __builtin_amdgcn_sched_barrier(0);              // one tile's 16 fp64 values in registers at a time
-        }
-      }
+        for (int cb = 0; cb < CB; ++cb)
+          if (t < nrb) flush_tile(part + ((int64_t)unit * nb * CB + (wave + SPAN_WAVES * t) * CB + cb) * 1024, acc[t][cb], first);
       first = false;
     }
   }
@@ -230,20 +187,14 @@ __global__ __launch_bounds__(256) void sums_reduce_kernel(const double* __restri
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t items = (int64_t)tiles * 1024;
   if (gid < items) {
-    const int tile = (int)(gid >> 10), e = (int)(gid & 1023);
+    const int tile = (int)(gid >> 10);
     const int rb = tile / cbn, cb = tile % cbn;
-    const int row = acc_row(e & 15, e >> 9), col = (e >> 4) & 31;      // e = 16 lane + register
+    int row, col;
+    acc_elem((int)(gid & 1023), row, col);
     const int cl = 32 * cb + col;
-    if (cl < c) {
-      double s = 0.0;
-      for (int u = 0; u < units; ++u) s += part[((int64_t)u * tiles + tile) * 1024 + e];
-      sums[(int64_t)cl * f + 32 * rb + row] = s;
-    }
+    if (cl < c) sums[(int64_t)cl * f + 32 * rb + row] = sum_over_spans(part, units, items, gid);
   } else if (gid - items < c) {
-    const int i = (int)(gid - items);
-    unsigned long long n = 0ull;
-    for (int u = 0; u < units; ++u) n += pcounts[(int64_t)u * VITTF_KMEANS_MAX_C + i];
-    counts[i] = (int64_t)n;
+    counts[gid - items] = (int64_t)sum_over_spans(pcounts, units, VITTF_KMEANS_MAX_C, gid - items);
   }
 }
 
@@ -253,7 +204,7 @@ static bool kmeans_c_ok(int32_t c) { return c >= 2 && c <= VITTF_KMEANS_MAX_C; }
 
 int vittf_kmeans_assign(const uint16_t* feat, int32_t f, int64_t nvox, const float* cent, const float* half_sq, int32_t c,
                         uint8_t* labels, float* best, void* stream) {
-  if (!feat || !cent || !labels || !gram_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return VITTF_ERR_INVALID_ARG;
+  if (!feat || !cent || !labels || !feat_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)cent & 3) || ((uintptr_t)half_sq & 3) || ((uintptr_t)best & 3)) return VITTF_ERR_INVALID_ARG;
   const int64_t wgs = (nvox + PJ_VOX - 1) / PJ_VOX;
   if (wgs > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
@@ -268,32 +219,32 @@ int vittf_kmeans_assign(const uint16_t* feat, int32_t f, int64_t nvox, const flo
 }
 
 size_t vittf_kmeans_sums_workspace_bytes(int32_t f, int64_t nvox, int32_t c) {
-  if (!gram_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return 0;
+  if (!feat_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return 0;
   const SumsPlan p = sums_plan(f, nvox, c);
-  return ((size_t)p.units * p.tiles * 1024 + (size_t)p.units * VITTF_KMEANS_MAX_C) * sizeof(double);
+  return ((size_t)p.span.units * p.tiles * 1024 + (size_t)p.span.units * VITTF_KMEANS_MAX_C) * sizeof(double);
 }
 
 int vittf_kmeans_sums(const uint16_t* feat, int32_t f, int64_t nvox, const uint8_t* labels, int32_t c, double* sums,
                       int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
-  if (!feat || !labels || !sums || !counts || !ws || !gram_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return VITTF_ERR_INVALID_ARG;
+  if (!feat || !labels || !sums || !counts || !ws || !feat_f_ok(f) || nvox < 1 || !kmeans_c_ok(c)) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)ws & 7)) return VITTF_ERR_INVALID_ARG;
   if (ws_bytes < vittf_kmeans_sums_workspace_bytes(f, nvox, c)) return VITTF_ERR_WORKSPACE;
   const SumsPlan p = sums_plan(f, nvox, c);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)ws;
-  unsigned long long* pcounts = (unsigned long long*)(part + (size_t)p.units * p.tiles * 1024);
-  const dim3 grid((unsigned)p.units);
+  unsigned long long* pcounts = (unsigned long long*)(part + (size_t)p.span.units * p.tiles * 1024);
+  const dim3 grid((unsigned)p.span.units);
   const bool al = rows_aligned(feat, nvox);
 #define KS_LAUNCH(AL, RBW, PRE, CB) \
-  hipLaunchKernelGGL((sums_kernel<AL, RBW, PRE, CB>), grid, dim3(KS_THREADS), 0, st, feat, f, nvox, labels, c, p.nb, p.runs_per_unit, part, pcounts)
+  hipLaunchKernelGGL((sums_kernel<AL, RBW, PRE, CB>), grid, dim3(SPAN_THREADS), 0, st, feat, f, nvox, labels, c, p.nb, p.span.runs_per_unit, part, pcounts)
 #define KS_PICK(RBW, PRE) \
   do { if (p.cbn == 1) { if (al) KS_LAUNCH(true, RBW, PRE, 1); else KS_LAUNCH(false, RBW, PRE, 1); } \
        else { if (al) KS_LAUNCH(true, RBW, PRE, 2); else KS_LAUNCH(false, RBW, PRE, 2); } } while (0)
-  if (f <= KS_NARROW) KS_PICK(KS_RBW_NARROW, KS_PRE_NARROW); else KS_PICK(KS_RBW_WIDE, KS_PRE_WIDE);
+  if (f <= SPAN_NARROW) KS_PICK(KS_RBW_NARROW, SPAN_PRE_NARROW); else KS_PICK(KS_RBW_WIDE, SPAN_PRE_WIDE);
 #undef KS_PICK
 #undef KS_LAUNCH
   const int64_t items = (int64_t)p.tiles * 1024 + c;
   hipLaunchKernelGGL(sums_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, part, pcounts, f, c, p.cbn, p.tiles,
-                     p.units, sums, counts);
+                     p.span.units, sums, counts);
   return vittf_check_launch();
 }

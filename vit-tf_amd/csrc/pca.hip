@@ -1,17 +1,15 @@
 // PCA reduction of an F-major fp16 feature volume [f][nvox] (the file layout of infer.py): the Gram matrix + row sums the
 // host turns into a basis (vit-tf_amd/pca.py basis_from_gram), and the projection onto that basis.
 //
-// vittf_feature_gram: gram = X X^T and sums = X 1 in fp64.  Both MFMA operands are rows of the same matrix and the reduction
-// runs along the rows, so a lane's 8 consecutive voxels of a row ARE an operand fragment of v_mfma_f32_32x32x16_f16: no
-// transpose.  Only the nb (nb + 1) / 2 upper 32 x 32 tiles (nb = f / 32) are computed.  For f <= 384 a workgroup of 8 waves
-// owns up to 80 of them (10 accumulator tiles per wave: f = 384 has 78, one workgroup group, the volume is read once); wider
-// f stages more rows per thread, keeps 6 tiles per wave and splits the tile list over several groups, each of which reads
-// the volume again.  A workgroup walks a span of voxels in steps of 32: all f rows of a step are staged
-// in LDS (through registers, one step ahead of the MFMAs), every wave reads its tiles' row blocks from there.
-//   * products of two fp16 values are exact in fp32; an fp32 accumulator covers at most VITTF_GRAM_RUN voxels, then it is
-//     added into the workgroup's private fp64 partial in the workspace (the first run writes, later runs read-add-write);
-//   * a second kernel sums the partials of the voxel spans in fp64 in span order and writes both triangles (a diagonal
-//     tile is mirrored from its own upper half, so gram is exactly symmetric); no floating-point atomics anywhere;
+// vittf_feature_gram: gram = X X^T and sums = X 1 in fp64, by the span reduction of span_rows.h with both MFMA operands
+// rows of the same staged matrix.  Only the nb (nb + 1) / 2 upper 32 x 32 tiles (nb = f / 32) are computed.  For f <= 384 a
+// workgroup of 8 waves owns up to 80 of them (10 accumulator tiles per wave: f = 384 has 78, one workgroup group, the volume
+// is read once); wider f stages more rows per thread, keeps 6 tiles per wave and splits the tile list over several groups,
+// each of which reads the volume again.
+//   * products of two fp16 values are exact in fp32, so an entry carries only the rounding of its fp32 runs;
+//   * the row sums are taken from the staged chunks as they are committed (group 0 only), flushed with the tiles;
+//   * the second kernel writes both triangles (a diagonal tile is mirrored from its own upper half, so gram is exactly
+//     symmetric);
 //   * rows that are not 16-byte aligned (nvox % 8, or an odd base address) take 2-byte loads; voxels past the end are zeros.
 //
 // vittf_feature_project: out[k][v] = fp16(sum_f comp[k][f] x[f][v] - offset[k]).  The reduction runs over f, so the volume
@@ -21,35 +19,23 @@
 // k padded with zero rows to 32 or 64; fp32 accumulation, one rounding to fp16; the volume is read once.  That loop is
 // project_scores in feat_rows.h, which the k-means assignment (kmeans.hip) shares.
 #include "vittf_common.h"
-#include "feat_rows.h"
+#include "span_rows.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ Gram
-constexpr int GR_THREADS = 512, GR_WAVES = 8;
-constexpr int GR_STEP = 32;                         // voxels per staged step: two MFMA k-steps
-constexpr int GR_ROW = 2 * GR_STEP + 16;            // LDS bytes per staged row (16 bytes of padding: odd number of 16-byte slots)
-constexpr int GR_MAXF = FEAT_MAXF;
-constexpr int GR_NARROW = 384;                      // f up to here: 10 accumulator tiles per wave, 3 staged chunks per thread
-constexpr int GR_SLOTS_NARROW = 10, GR_SLOTS_WIDE = 6;   // accumulator tiles per wave; x GR_WAVES = tiles per workgroup
+constexpr int GR_SLOTS_NARROW = 10, GR_SLOTS_WIDE = 6;   // accumulator tiles per wave (f <= SPAN_NARROW, wider); x SPAN_WAVES = tiles per workgroup
 constexpr int GR_UNITS = 128;                       // most voxel spans (over all tile groups): bounds the workspace
-constexpr int GR_PRE_NARROW = GR_NARROW * (GR_STEP / 8) / GR_THREADS;   // 16-byte chunks a thread stages per step, at most
-constexpr int GR_PRE_WIDE = GR_MAXF * (GR_STEP / 8) / GR_THREADS;
-static_assert(VITTF_GRAM_RUN % GR_STEP == 0 && VITTF_GRAM_RUN <= 4096, "an fp32 accumulator covers whole steps");
-static_assert(GR_THREADS % (GR_STEP / 8) == 0, "a thread's chunk column is the same for all its rows");
 
-struct GramPlan { int nb, pairs, groups, units; int64_t runs_per_unit; };
+struct GramPlan { int nb, pairs, groups; SpanPlan span; };
 
 static GramPlan gram_plan(int f, int64_t nvox) {
   GramPlan p;
   p.nb = f / 32;
   p.pairs = p.nb * (p.nb + 1) / 2;
-  const int per_group = GR_WAVES * (f <= GR_NARROW ? GR_SLOTS_NARROW : GR_SLOTS_WIDE);
+  const int per_group = SPAN_WAVES * (f <= SPAN_NARROW ? GR_SLOTS_NARROW : GR_SLOTS_WIDE);
   p.groups = (p.pairs + per_group - 1) / per_group;
-  const int max_units = GR_UNITS / p.groups > 0 ? GR_UNITS / p.groups : 1;
-  const int64_t runs = (nvox + VITTF_GRAM_RUN - 1) / VITTF_GRAM_RUN;
-  p.runs_per_unit = (runs + max_units - 1) / max_units;
-  p.units = (int)((runs + p.runs_per_unit - 1) / p.runs_per_unit);
+  p.span = span_plan(nvox, GR_UNITS / p.groups > 0 ? GR_UNITS / p.groups : 1);
   return p;
 }
 
@@ -69,32 +55,28 @@ __device__ __forceinline__ float sum8_f16(uint4 c) {
   return s;
 }
 
-// grid: units x groups.  part: fp64 [units][pairs][1024] (a tile in accumulator order: register r of lane l at 16 l + r),
-// psums: fp64 [units][f].
+// grid: units x groups.  part: fp64 [units][pairs][1024] (tiles in accumulator order), psums: fp64 [units][f].
 // GR_PRE: 16-byte chunks a thread stages per step = rows the slab holds / 128
 template <bool ALIGNED, int GR_SLOTS, int GR_PRE>
-__global__ __launch_bounds__(GR_THREADS) void gram_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox, int nb,
-                                                          int pairs, int units, int64_t runs_per_unit,
-                                                          double* __restrict__ part, double* __restrict__ psums) {
-  __shared__ __attribute__((aligned(16))) char slab[GR_PRE * GR_THREADS / (GR_STEP / 8) * GR_ROW];   // 30 KB (f <= 384) or 80 KB
+__global__ __launch_bounds__(SPAN_THREADS) void gram_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox, int nb,
+                                                            int pairs, int units, int64_t runs_per_unit,
+                                                            double* __restrict__ part, double* __restrict__ psums) {
+  __shared__ __attribute__((aligned(16))) char slab[span_slab_bytes(GR_PRE)];   // 30 KB (f <= 384) or 80 KB
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, l31 = lane & 31;
   const int unit = blockIdx.x % units, group = blockIdx.x / units;
-  const int64_t vbeg = (int64_t)unit * runs_per_unit * VITTF_GRAM_RUN;
-  const int64_t vend = vbeg + runs_per_unit * VITTF_GRAM_RUN < nvox ? vbeg + runs_per_unit * VITTF_GRAM_RUN : nvox;
-  const int64_t nsteps = (vend - vbeg + GR_STEP - 1) / GR_STEP;
+  const Span span(unit, runs_per_unit, nvox);
 
   // the wave's tiles: GR_SLOTS consecutive entries of the tile list, so that neighbours share their row block
-  const int p0 = (group * GR_WAVES + wave) * GR_SLOTS;
+  const int p0 = (group * SPAN_WAVES + wave) * GR_SLOTS;
   const int nslots = pairs - p0 < 0 ? 0 : (pairs - p0 < GR_SLOTS ? pairs - p0 : GR_SLOTS);
   int abase[GR_SLOTS], bbase[GR_SLOTS];
 #pragma unroll
   for (int t = 0; t < GR_SLOTS; ++t) {
     int bi = 0, bj = 0;
     if (t < nslots) gram_pair(p0 + t, nb, bi, bj);
-    abase[t] = __builtin_amdgcn_readfirstlane(bi * 32 * GR_ROW);
-    bbase[t] = __builtin_amdgcn_readfirstlane(bj * 32 * GR_ROW);
+    abase[t] = __builtin_amdgcn_readfirstlane(bi * 32 * SPAN_ROW);
+    bbase[t] = __builtin_amdgcn_readfirstlane(bj * 32 * SPAN_ROW);
   }
   f32x16_t acc[GR_SLOTS];
 #pragma unroll
@@ -102,36 +84,21 @@ __global__ __launch_bounds__(GR_THREADS) void gram_kernel(const unsigned short* 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-  // staging: 16-byte chunk (i & 3) of row (i >> 2), i = tid + GR_THREADS k
-  const int nchunks = f * (GR_STEP / 8);
-  const int my_chunk = tid & (GR_STEP / 8 - 1);
-  uint4 pre[GR_PRE];
-  float rowsum[GR_PRE];
+  RowStager<ALIGNED, GR_PRE> rows(feat, f, nvox, span.vbeg);
+  float rowsum[GR_PRE];                               // of the thread's chunks, since the last flush
 #pragma unroll
   for (int k = 0; k < GR_PRE; ++k) rowsum[k] = 0.f;
-  auto prefetch = [&](int64_t step) {
-    const int64_t v = vbeg + step * GR_STEP + 8 * my_chunk;
-#pragma unroll
-    for (int k = 0; k < GR_PRE; ++k) {
-      const int i = tid + GR_THREADS * k;
-      if (i < nchunks) pre[k] = gram_load8<ALIGNED>(feat + (int64_t)(i >> 2) * nvox, v, nvox);
-    }
-  };
-  const int frag_off = l31 * GR_ROW + h * 16;
+  const int frag_off = span_frag_off(lane);
   bool first = true;
-  prefetch(0);
-  for (int64_t step = 0; step < nsteps; ++step) {
+  rows.prefetch(0);
+  for (int64_t step = 0; step < span.nsteps; ++step) {
     __syncthreads();                                  // the previous step's fragments have been read
+    rows.commit(slab);
 #pragma unroll
-    for (int k = 0; k < GR_PRE; ++k) {
-      const int i = tid + GR_THREADS * k;
-      if (i < nchunks) {
-        *reinterpret_cast<uint4*>(slab + (i >> 2) * GR_ROW + 16 * my_chunk) = pre[k];
-        rowsum[k] += sum8_f16(pre[k]);
-      }
-    }
+    for (int k = 0; k < GR_PRE; ++k)
+      if (rows.mine(k)) rowsum[k] += sum8_f16(rows.pre[k]);
     __syncthreads();
-    if (step + 1 < nsteps) prefetch(step + 1);
+    if (step + 1 < span.nsteps) rows.prefetch(step + 1);
     s16x8_t a0 = {}, a1 = {};
 #pragma unroll
     for (int t = 0; t < GR_SLOTS; ++t) {            // (a slot past the wave's last tile computes tile (0, 0) and is never flushed)
@@ -144,35 +111,18 @@ __global__ __launch_bounds__(GR_THREADS) void gram_kernel(const unsigned short* 
       acc[t] = mfma32<VITTF_FP16>(a0, b0, acc[t]);
       acc[t] = mfma32<VITTF_FP16>(a1, b1, acc[t]);
     }
-    // the end of a run of VITTF_GRAM_RUN voxels (or of the span): fp32 -> the workgroup's fp64 partial
-    if ((step + 1) % (VITTF_GRAM_RUN / GR_STEP) == 0 || step + 1 == nsteps) {
+    if (span.run_ends(step)) {
 #pragma unroll
-      for (int t = 0; t < GR_SLOTS; ++t) {
-        if (t < nslots) {
-          unsigned loff = 16 * lane;                      // 128 bytes per lane
-          asm volatile("" : "+v"(loff));                  // (keeps the 160 store addresses from being formed, and spilled, ahead of the loop)
-          double* dst = part + ((int64_t)unit * pairs + p0 + t) * 1024 + loff;
-          if (first) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[r] = (double)acc[t][r];
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[r] += (double)acc[t][r];
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        }
-        __builtin_amdgcn_sched_barrier(0);              // one tile's 16 fp64 values in registers at a time
-      }
+      for (int t = 0; t < GR_SLOTS; ++t)
+        if (t < nslots) flush_tile(part + ((int64_t)unit * pairs + p0 + t) * 1024, acc[t], first);
       if (group == 0) {
 #pragma unroll
         for (int k = 0; k < GR_PRE; ++k) {
           float s = rowsum[k];
           s += __shfl_xor(s, 1);
           s += __shfl_xor(s, 2);
-          const int i = tid + GR_THREADS * k;
-          if (i < nchunks && my_chunk == 0) {
-            double* dst = psums + (int64_t)unit * f + (i >> 2);
+          if (rows.mine(k) && rows.chunk() == 0) {
+            double* dst = psums + (int64_t)unit * f + rows.row(k);
             *dst = first ? (double)s : *dst + (double)s;
           }
           rowsum[k] = 0.f;
@@ -190,22 +140,17 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restri
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t tiles = (int64_t)pairs * 1024;
   if (gid < tiles) {
-    const int p = (int)(gid >> 10), e = (int)(gid & 1023);
-    int bi, bj;
-    gram_pair(p, nb, bi, bj);
-    const int row = acc_row(e & 15, e >> 9), col = (e >> 4) & 31;      // e = 16 lane + register
-    double s = 0.0;
-    for (int u = 0; u < units; ++u) s += part[((int64_t)u * pairs + p) * 1024 + e];
+    int bi, bj, row, col;
+    gram_pair((int)(gid >> 10), nb, bi, bj);
+    acc_elem((int)(gid & 1023), row, col);
+    const double s = sum_over_spans(part, units, tiles, gid);
     if (bi != bj || row <= col) {
       const int i = 32 * bi + row, j = 32 * bj + col;
       gram[(int64_t)i * f + j] = s;
       gram[(int64_t)j * f + i] = s;
     }
   } else if (gid - tiles < f) {
-    const int i = (int)(gid - tiles);
-    double s = 0.0;
-    for (int u = 0; u < units; ++u) s += psums[(int64_t)u * f + i];
-    sums[i] = s;
+    sums[gid - tiles] = sum_over_spans(psums, units, f, gid - tiles);
   }
 }
 
@@ -237,36 +182,36 @@ __global__ __launch_bounds__(PJ_THREADS) void project_kernel(const unsigned shor
 }  // namespace
 
 size_t vittf_feature_gram_workspace_bytes(int32_t f, int64_t nvox) {
-  if (!gram_f_ok(f) || nvox < 1) return 0;
+  if (!feat_f_ok(f) || nvox < 1) return 0;
   const GramPlan p = gram_plan(f, nvox);
-  return ((size_t)p.units * p.pairs * 1024 + (size_t)p.units * f) * sizeof(double);
+  return ((size_t)p.span.units * p.pairs * 1024 + (size_t)p.span.units * f) * sizeof(double);
 }
 
 int vittf_feature_gram(const uint16_t* feat, int32_t f, int64_t nvox, double* gram, double* sums, void* ws, size_t ws_bytes,
                        void* stream) {
-  if (!feat || !gram || !sums || !ws || !gram_f_ok(f) || nvox < 1) return VITTF_ERR_INVALID_ARG;
+  if (!feat || !gram || !sums || !ws || !feat_f_ok(f) || nvox < 1) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)gram & 7) || ((uintptr_t)sums & 7) || ((uintptr_t)ws & 7)) return VITTF_ERR_INVALID_ARG;
   if (ws_bytes < vittf_feature_gram_workspace_bytes(f, nvox)) return VITTF_ERR_WORKSPACE;
   const GramPlan p = gram_plan(f, nvox);
   hipStream_t st = (hipStream_t)stream;
   double* part = (double*)ws;
-  double* psums = part + (size_t)p.units * p.pairs * 1024;
-  const dim3 grid((unsigned)(p.units * p.groups));
+  double* psums = part + (size_t)p.span.units * p.pairs * 1024;
+  const dim3 grid((unsigned)(p.span.units * p.groups));
   const bool al = rows_aligned(feat, nvox);
 #define GR_LAUNCH(AL, SLOTS, PRE) \
-  hipLaunchKernelGGL((gram_kernel<AL, SLOTS, PRE>), grid, dim3(GR_THREADS), 0, st, feat, f, nvox, p.nb, p.pairs, p.units, p.runs_per_unit, part, psums)
-  if (f <= GR_NARROW) { if (al) GR_LAUNCH(true, GR_SLOTS_NARROW, GR_PRE_NARROW); else GR_LAUNCH(false, GR_SLOTS_NARROW, GR_PRE_NARROW); }
-  else { if (al) GR_LAUNCH(true, GR_SLOTS_WIDE, GR_PRE_WIDE); else GR_LAUNCH(false, GR_SLOTS_WIDE, GR_PRE_WIDE); }
+  hipLaunchKernelGGL((gram_kernel<AL, SLOTS, PRE>), grid, dim3(SPAN_THREADS), 0, st, feat, f, nvox, p.nb, p.pairs, p.span.units, p.span.runs_per_unit, part, psums)
+  if (f <= SPAN_NARROW) { if (al) GR_LAUNCH(true, GR_SLOTS_NARROW, SPAN_PRE_NARROW); else GR_LAUNCH(false, GR_SLOTS_NARROW, SPAN_PRE_NARROW); }
+  else { if (al) GR_LAUNCH(true, GR_SLOTS_WIDE, SPAN_PRE_WIDE); else GR_LAUNCH(false, GR_SLOTS_WIDE, SPAN_PRE_WIDE); }
 #undef GR_LAUNCH
   const int64_t items = (int64_t)p.pairs * 1024 + f;
   hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, part, psums, f, p.nb, p.pairs,
-                     p.units, gram, sums);
+                     p.span.units, gram, sums);
   return vittf_check_launch();
 }
 
 int vittf_feature_project(const uint16_t* feat, int32_t f, int64_t nvox, const float* comp, const float* offset, int32_t k,
                           uint16_t* out, void* stream) {
-  if (!feat || !comp || !out || !gram_f_ok(f) || nvox < 1 || k < 1 || k > VITTF_PCA_MAX_K) return VITTF_ERR_INVALID_ARG;
+  if (!feat || !comp || !out || !feat_f_ok(f) || nvox < 1 || k < 1 || k > VITTF_PCA_MAX_K) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)out & 1) || ((uintptr_t)comp & 3) || ((uintptr_t)offset & 3)) return VITTF_ERR_INVALID_ARG;
   const int64_t wgs = (nvox + PJ_VOX - 1) / PJ_VOX;
   if (wgs > 0x7fffffff) return VITTF_ERR_INVALID_ARG;

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pca import _as_matrix, _np, _on_device
+from ._featvol import _as_matrix, _np, _on_device, workspace
 
 Clustering = namedtuple('Clustering', ['centroids', 'counts', 'inertia', 'inertia_history', 'n_iter', 'converged'])
 Clustering.__doc__ = """centroids fp32 [c][F] (numbered by descending voxel count), counts int64 [c] and inertia (fp64 scalar
@@ -63,8 +63,7 @@ def cluster_sums(feat, labels, c):
     lab = lab.to(x.device).contiguous()
     sums = torch.empty((c, f), dtype=torch.float64, device=x.device)
     counts = torch.empty((c,), dtype=torch.int64, device=x.device)
-    ws_bytes = lib.vittf_kmeans_sums_workspace_bytes(f, nvox, c)
-    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=x.device)
+    ws, ws_bytes = workspace(lib.vittf_kmeans_sums_workspace_bytes(f, nvox, c), x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.vittf_kmeans_sums(_lib.ptr(x), f, nvox, _lib.ptr(lab), c, _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(ws),
                                          ws_bytes, _lib.stream_ptr()), 'vittf_kmeans_sums')

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._featvol import _as_matrix, _np, _on_device, workspace
 
 Basis = namedtuple('Basis', ['components', 'mean', 'explained_variance', 'total_variance', 'center', 'offset'])
 Basis.__doc__ = """components fp32 [k][F] (orthonormal rows, descending variance), mean fp32 [F] (zeros when not centred),
@@ -30,8 +31,7 @@ def feature_gram(feat):
     f, nvox = x.shape
     gram = torch.empty((f, f), dtype=torch.float64, device=x.device)
     sums = torch.empty((f,), dtype=torch.float64, device=x.device)
-    ws_bytes = lib.vittf_feature_gram_workspace_bytes(f, nvox)
-    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=x.device)
+    ws, ws_bytes = workspace(lib.vittf_feature_gram_workspace_bytes(f, nvox), x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.vittf_feature_gram(_lib.ptr(x), f, nvox, _lib.ptr(gram), _lib.ptr(sums), _lib.ptr(ws), ws_bytes,
                                           _lib.stream_ptr()), 'vittf_feature_gram')
@@ -137,33 +137,3 @@ def rgb_volume(reduced):
         scale = 255.0 / (hi - lo) if hi > lo else 0.0
         out[..., c] = np.clip(np.rint((ch - lo) * scale), 0, 255).astype(np.uint8)
     return out
-
-
-def _np(t, dtype):
-    return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t), dtype=dtype)
-
-
-def _on_device(feat):
-    """The volume as a contiguous fp16 device tensor (F, ...) with the features in front and any number of voxel dimensions
-    behind them (vt.feature_volume squeezes singleton ones away); one that already is such a tensor is used where it lies."""
-    t = feat if isinstance(feat, torch.Tensor) else torch.as_tensor(np.asarray(feat))
-    if t.ndim < 2:
-        raise ValueError(f'features must be (F, ...) with at least one voxel dimension, got {tuple(t.shape)}')
-    if t.is_cuda and t.dtype == torch.float16 and t.is_contiguous():
-        return t
-    return t.to(device=t.device if t.is_cuda else _device(), dtype=torch.float16).contiguous()
-
-
-def _as_matrix(feat):
-    x = _on_device(feat)
-    x = x.reshape(x.shape[0], -1)
-    f, nvox = x.shape
-    if f % 32 or not 32 <= f <= 1024:
-        raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
-    if nvox < 1:
-        raise ValueError('the volume has no voxels')
-    return x
-
-
-def _device():
-    return torch.device('cuda', torch.cuda.current_device())
