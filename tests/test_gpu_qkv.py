@@ -2,6 +2,8 @@
 
 * vittf_gemm_kfeat_parts: every requested third bit-equal to vittf_gemm(EPI_KFEAT) on that third's weights, nothing
   written behind an output or into the output of an unset bit, bad masks and NULL pointers refused.
+* the K-feature epilogue of both GEMM kernels (fp16 operands) bit-equal to the plain bias epilogue with the dropped rows taken
+  out on the host: vittf_gemm_kfeat_parts_reg with and without register rows, and vittf_gemm(EPI_KFEAT).
 * vittf_vit_qkv_features: each third bit-equal to vittf_vit_k_features(part) on the engine's four projection paths.
 * compute_qkv(return_keys=['q','k','v']) runs the ViT once: as many patch-embedding and K-projection launches as 'k'.
 * vittf_pool_slices3d: bit-equal to the CPU F.adaptive_avg_pool3d of the same fp16 features.
@@ -127,6 +129,52 @@ def test_gemm_kfeat_parts_output_beyond_4_gib(gpu):
         torch.cuda.synchronize()
         assert torch.equal(bufs[p][:n_out], ref), p
         del ref
+
+
+@pytest.mark.parametrize('d,k,tokens,batch,kernel', [(128, 128, 17, 9, 'gemm_kernel'), (256, 768, 131, 5, 'gemm_pp_kernel')])
+def test_gemm_kfeat_bit_equal_to_bias_epilogue(gpu, d, k, tokens, batch, kernel):
+    """The K-feature output of both kernels, through vittf_gemm_kfeat_parts_reg and through vittf_gemm(EPI_KFEAT), against an
+    oracle that shares no epilogue code with it: vittf_gemm(EPI_BIAS) of the same kernel family over the whole [3 d][k]
+    projection, the rows tok <= n_reg of every slice dropped on the host, cut into thirds.  With fp16 operands both epilogues
+    round the same fp32 sums to fp16: bit-equal.  (The last row tile is partial and a row tile holds several slices.)"""
+    lib = vt._lib.load()
+    g = torch.Generator().manual_seed(d + tokens)
+    rows = tokens * batch
+    a = torch.randn((rows, k), generator=g).to(gpu, torch.float16)
+    w = (torch.randn((3 * d, k), generator=g) * k ** -0.5).to(gpu, torch.float16)
+    bias = torch.randn(3 * d, generator=g).to(gpu)
+    st = vt._lib.stream_ptr()
+    full = torch.empty((rows, 3 * d), dtype=torch.int16, device=gpu)
+    assert lib.vittf_gemm(vt._lib.ptr(a), vt._lib.ptr(w), vt._lib.ptr(bias), vt._lib.ptr(full), rows, 3 * d, k,
+                          vt._lib.EPI_BIAS, 0, vt._lib.FP16, st) == 0
+    torch.cuda.synchronize()
+    tok = torch.arange(rows, device=gpu) % tokens
+    tail = 4 * d                                       # guard rows behind every output
+    for n_reg in (0, 4):
+        kept = full[tok > n_reg]
+        want = [kept[:, p * d:(p + 1) * d].reshape(-1) for p in range(3)]
+        n_out = (rows - batch * (1 + n_reg)) * d
+        assert want[0].numel() == n_out
+        for mask in (2, 5, 7):
+            bufs = [_canary_buf(n_out, tail, gpu) for _ in range(3)]
+            assert lib.vittf_gemm_kfeat_parts_reg(vt._lib.ptr(a), vt._lib.ptr(w), vt._lib.ptr(bias), rows, d, k, tokens, n_reg,
+                                                  mask, *(vt._lib.ptr(b) for b in bufs), vt._lib.FP16, st) == 0
+            torch.cuda.synchronize()
+            assert vt._lib.kernel_name('gemm') == kernel
+            for p in range(3):
+                if (mask >> p) & 1:
+                    assert torch.equal(bufs[p][:n_out], want[p]), (n_reg, mask, p)
+                    assert bool((bufs[p][n_out:] == CANARY).all()), (n_reg, mask, p, 'guard rows')
+                else:
+                    assert bool((bufs[p] == CANARY).all()), (n_reg, mask, p, 'output of an unset bit')
+        if n_reg == 0:
+            for p in range(3):
+                o = _canary_buf(n_out, tail, gpu)
+                assert lib.vittf_gemm(vt._lib.ptr(a), vt._lib.ptr(w[p * d:]), vt._lib.ptr(bias[p * d:]), vt._lib.ptr(o), rows,
+                                      d, k, vt._lib.EPI_KFEAT, tokens, vt._lib.FP16, st) == 0
+                torch.cuda.synchronize()
+                assert torch.equal(o[:n_out], want[p]), ('single third', p)
+                assert bool((o[n_out:] == CANARY).all()), ('single third', p, 'guard rows')
 
 
 def _engine_case(gpu, arch, seed, dt='fp16', **kw):

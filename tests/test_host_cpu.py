@@ -320,6 +320,30 @@ def test_span_kernel_register_contract(tmp_path):
             assert int(re.search(r'Occupancy \[waves/SIMD\]: (\d+)', l).group(1)) >= floor[0], l
 
 
+def test_gemm_kernels_have_one_kfeat_epilogue(tmp_path):
+    """csrc/gemm.hip and csrc/gemm_pp.hip carry ONE K-feature epilogue each (the internal ids 100 / 101, which
+    vittf_gemm(VITTF_EPI_KFEAT) forwards to with one slot): no instantiation with the public id 3, every other epilogue in bf16
+    and fp16, at the waves per SIMD the kernels are laid out for and without scratch -- but for the 8 bytes per lane the fp8 qkv
+    epilogue (id 100 of gemm_pp.hip) keeps.  Read from the resource-usage remarks alone."""
+    import re
+    import shutil
+    if not shutil.which('/opt/rocm/bin/hipcc'):
+        pytest.skip('no hipcc')
+    for src, kern, ids, occupancy, scratch in (('gemm.hip', 'gemm_kernel', (0, 1, 2, 4, 100), 4, {}),
+                                               ('gemm_pp.hip', 'gemm_pp_kernel', (0, 1, 2, 4, 100, 101), 2, {100: 8})):
+        r = _kernel_asm(src, tmp_path)
+        assert r.returncode == 0, r.stdout + r.stderr
+        usage = {}
+        for l in r.stdout.splitlines():
+            m = re.search(r'\d+%sILi(\d+)ELi(\d+)EE' % kern, l)
+            if m and 'ScratchSize' in l:
+                usage[(int(m.group(1)), int(m.group(2)))] = l
+        assert sorted(usage) == sorted((dt, e) for dt in (_lib.BF16, _lib.FP16) for e in ids), sorted(usage)
+        for (dt, e), l in usage.items():
+            assert 'Occupancy [waves/SIMD]: %d ' % occupancy in l, l
+            assert int(re.search(r'ScratchSize \[bytes/lane\]: (\d+)', l).group(1)) <= scratch.get(e, 0), l
+
+
 def test_window_goldens_cover_the_fullsize_tests():
     """tests/golden/windows512.npz (made by tests/golden/make_window_goldens.py from the CPU oracle) holds every pooled window the
     full-size GPU tests compare with: fp16, every 4th feature row / column of a (D, 64, 64) window, finite, not constant."""

@@ -23,6 +23,7 @@
 //     past the end are clamped on load and their stores are guarded
 //   * workgroups are remapped so that the q-tiles of one (slice, head) share an XCD's L2 (K/V re-reads)
 #include "attn_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 
@@ -277,9 +278,6 @@ __global__ __launch_bounds__(256, 4) void attn_kernel(const unsigned short* __re
 }
 
 }  // namespace
-
-int vittf_attention_pp64(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
-                         hipStream_t st);                                                          // attention_pp64.hip
 
 extern "C" int vittf_attention(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads,
                                int32_t dtype, int32_t q_prescaled, void* stream) {

@@ -35,6 +35,7 @@
 // blocks run along the KEYS: they cross the rows a GEMM tile produces); its absmax comes from that GEMM's epilogue and only
 // the v third goes through the quantise + re-lay kernel (vittf_attention_fp8_rows).
 #include "attn_common.h"
+#include "vittf_internal.h"
 
 namespace {
 

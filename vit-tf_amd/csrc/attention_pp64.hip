@@ -22,6 +22,7 @@
 //   * S^T = K Q^T so a lane owns one query column; the P registers feed O^T = V^T P^T directly; V^T fragments by
 //     ds_read_b64_tr_b16; the ragged last tile is range-checked by the buffer descriptor and masked to -inf.
 #include "attn_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 

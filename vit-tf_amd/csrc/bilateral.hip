@@ -17,7 +17,7 @@
 // partials every workgroup then adds in the same fixed order, so dot products are deterministic; convergence latched
 // in a device flag, no host round trip).  All arithmetic that the reference does in fp64 is fp64 here;
 // the fp32 parts (resize, Sobel) use unfused multiply / add in the CPU operators' order.
-#include "vittf_common.h"
+#include "vittf_internal.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -581,7 +581,6 @@ __global__ __launch_bounds__(BT) void quantize_kernel(const float* __restrict__ 
   out[i] = (unsigned char)((long long)s & 255);     // truncate toward zero, then wrap like the x86 cast
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 unsigned blocks_for(int64_t n) { return (unsigned)((n + BT - 1) / BT); }
 
 struct Layout {

@@ -13,7 +13,7 @@
 //   O    h16  [rows][D]
 //   (fp8 attention operands, opt-in)   tile counter of the block-tail / qkv kernels (4 bytes; one workspace = one stream)
 // Everything is enqueued on the caller's stream; nothing synchronises with the host.
-#include "vittf_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 #include <vector>
@@ -32,8 +32,6 @@ hipEvent_t prof_event() {
   (void)hipEventCreate(&e);
   return e;
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct WsLayout {
   size_t x, h, qkv, o, fp8, fp8_bytes, tile_ctr, total;

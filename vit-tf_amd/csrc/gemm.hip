@@ -14,7 +14,11 @@
 //     computes C^T: a lane then owns ONE activation row and 4 consecutive output columns per register quad,
 //     so bias loads are float4 and stores are 8 B (16-bit out) or 16 B (fp32 residual) per lane
 //   * workgroups are remapped so that consecutive tiles (which share the A panel) run on one XCD's L2
-#include "vittf_common.h"
+//
+// This file also holds the dispatch of every linear (vittf_gemm, vittf_gemm_residual_ln, vittf_gemm_kfeat_parts): which of
+// the three GEMM kernels takes a shape is asked of the coverage predicates beside the other two (vittf_internal.h); the tiles
+// here take the rest.  One K-feature epilogue (EPI_KFEAT_PARTS): vittf_gemm(VITTF_EPI_KFEAT) is its one-slot launch.
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 
@@ -40,10 +44,11 @@ __device__ __forceinline__ void stage_tile(const T* __restrict__ src, int64_t ld
   for (int i = 0; i < 4; ++i) lds_dma16(rsrc, lds_tile + i * 4096, voff[i], k0 * 2);
 }
 
-// Several thirds of attn.qkv in one launch (vittf_gemm_kfeat_parts): W / bias are the whole [n = 3 d][k] / [3 d] of the
-// projection and the grid covers only the column tiles of the requested thirds, slot s of them = third part[s]; each third
-// leaves with the K-feature epilogue into its own [rows - CLS rows][d] output.  A tile reads the same weight rows and bias
-// as the single-third launch on that third's weights: the same bits.
+// The K-feature epilogue (the hooked tensor: fp16 values, the leading rows of every slice dropped), for several thirds of
+// attn.qkv in one launch (vittf_gemm_kfeat_parts): W / bias are the whole [n = 3 d][k] / [3 d] of the projection and the
+// grid covers only the column tiles of the requested thirds, slot s of them = third part[s]; each third leaves into its own
+// [rows - dropped rows][d] output.  vittf_gemm(VITTF_EPI_KFEAT) is the same launch with one slot: its [n][k] weights as
+// third 0 of width d = n, drop = 1.  A tile's bits depend on its weight rows, bias and activations, not on the slot.
 constexpr int EPI_KFEAT_PARTS = 100;      // (internal epilogue id)
 struct KfeatParts {
   unsigned short* out[3];   // by third (q, k, v)
@@ -189,7 +194,7 @@ __global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __re
             v0 *= sc; v1 *= sc; v2 *= sc; v3 *= sc;
           }
           uint2 pk;
-          if constexpr (EPI == VITTF_EPI_KFEAT || EPI == EPI_KFEAT_PARTS) {
+          if constexpr (EPI == EPI_KFEAT_PARTS) {
             pk.x = pack2_h16<VITTF_FP16>(v0, v1);
             pk.y = pack2_h16<VITTF_FP16>(v2, v3);
           } else {
@@ -208,13 +213,12 @@ __global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __re
       const int64_t m = m0 + rl;
       if (m >= rows) continue;
       int64_t orow = m;
-      if constexpr (EPI == VITTF_EPI_KFEAT || EPI == EPI_KFEAT_PARTS) {
+      if constexpr (EPI == EPI_KFEAT_PARTS) {
         const int64_t b = m / tokens;
         const int tok = (int)(m - b * tokens);
-        // CLS row dropped (infer.py:202 k[:, 1:]); the several-thirds form also drops the register rows behind it
-        const int drop = EPI == EPI_KFEAT_PARTS ? kp.drop : 1;
-        if (tok < drop) continue;
-        orow = b * (tokens - drop) + tok - drop;
+        // CLS row dropped (infer.py:202 k[:, 1:]), and the register rows behind it
+        if (tok < kp.drop) continue;
+        orow = b * (tokens - kp.drop) + tok - kp.drop;
       }
       const uint4 v = *reinterpret_cast<const uint4*>(smem + rl * CS + (tid & 15) * 16);
       if constexpr (EPI == EPI_KFEAT_PARTS)
@@ -225,12 +229,14 @@ __global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __re
   }
 }
 
+// kp: the K-feature launch (n = the weight rows W holds, part_tiles = the column tiles of its slots), else epi's epilogue
 template <int DT>
 int launch_gemm(const void* a, const void* w, const float* bias, void* out, int64_t rows, int n, int k, int epi,
-                int tokens, hipStream_t st, KfeatParts kp = KfeatParts{}, int part_tiles = 0) {
-  // (EPI_KFEAT_PARTS: n = 3 d weight rows, part_tiles = the requested thirds' column tiles)
-  const int m_tiles = (int)((rows + BM - 1) / BM), n_tiles = epi == EPI_KFEAT_PARTS ? part_tiles : n / BN;
-  const int total = m_tiles * n_tiles;
+                int tokens, hipStream_t st, const KfeatParts* kp = nullptr, int part_tiles = 0) {
+  const int64_t m_tiles = (rows + BM - 1) / BM;
+  const int n_tiles = kp ? part_tiles : n / BN;
+  if (m_tiles * n_tiles > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
+  const int total = (int)(m_tiles * n_tiles);
   // one stage, not two: +16 % on the K = 384 shapes, whose six K steps are too short for a double buffer to pay
   const size_t lds = (size_t)BM * (BN * 2 + 16);   // 32 KB stage / padded C tile (16-bit: 128 x 272 B; fp32 half tile: 128 x 272 B)
   const unsigned short* A = (const unsigned short*)a;
@@ -238,13 +244,12 @@ int launch_gemm(const void* a, const void* w, const float* bias, void* out, int6
 #define VITTF_GEMM_CASE(E)                                                                                   \
   case E:                                                                                                    \
     hipLaunchKernelGGL((gemm_kernel<DT, E>), dim3(total), dim3(256), lds, st, A, Wp, bias, out, rows, n, k,  \
-                       tokens, n_tiles, total, kp);                                                          \
+                       tokens, n_tiles, total, kp ? *kp : KfeatParts{});                                     \
     break;
-  switch (epi) {
+  switch (kp ? EPI_KFEAT_PARTS : epi) {
     VITTF_GEMM_CASE(VITTF_EPI_BIAS)
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_GELU)
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_RESIDUAL)
-    VITTF_GEMM_CASE(VITTF_EPI_KFEAT)
     VITTF_GEMM_CASE(VITTF_EPI_BIAS_QKV)
     VITTF_GEMM_CASE(EPI_KFEAT_PARTS)
     default: return VITTF_ERR_INVALID_ARG;
@@ -253,39 +258,49 @@ int launch_gemm(const void* a, const void* w, const float* bias, void* out, int6
   return vittf_check_launch();
 }
 
+// the K-feature launch of the thirds in `mask` (third p of w [.. ][k] -> outs[p], `drop` leading rows of a slice dropped)
+int launch_gemm_kfeat(const void* a, const void* w, const float* bias, int64_t rows, int d, int k, int tokens, int drop,
+                      int mask, int w_rows, void* const outs[3], int dtype, hipStream_t st) {
+  KfeatParts kp{};
+  int slots = 0;
+  for (int p = 0; p < 3; ++p) {
+    kp.out[p] = (unsigned short*)outs[p];
+    if ((mask >> p) & 1) kp.part[slots++] = p;
+  }
+  kp.d = d;
+  kp.drop = drop;
+  const int part_tiles = slots * (d / BN);
+  if (dtype == VITTF_BF16) return launch_gemm<VITTF_BF16>(a, w, bias, nullptr, rows, w_rows, k, 0, tokens, st, &kp, part_tiles);
+  if (dtype == VITTF_FP16) return launch_gemm<VITTF_FP16>(a, w, bias, nullptr, rows, w_rows, k, 0, tokens, st, &kp, part_tiles);
+  return VITTF_ERR_INVALID_ARG;
+}
+
+// Residual linears with 384 / 768 output columns (ViT-S / ViT-B proj and fc2) ask the whole-row kernel of gemm_rows.hip
+// first -- except 768 columns from K = 3072 on (ViT-B fc2), which ask the persistent kernel first: the LayerNorm behind
+// it then runs as its own launch instead of in the whole-row kernel's epilogue, 1.56 against 1.87 ms per 64 slices.
+bool rows_first(int n, int k) { return n == 384 || (n == 768 && k < 3072); }
+
 }  // namespace
 
-int vittf_gemm_rows(const void* a, const void* w, const float* bias, float* x, int64_t rows, int32_t n, int32_t k,
-                    int32_t dtype, const float* ln_g, const float* ln_b, float ln_eps, void* h, hipStream_t st);   // gemm_rows.hip
-
-int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
-                  int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st);   // gemm_pp.hip; 1 = not covered
-
-int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
-                              int32_t tokens, int32_t n_reg, int32_t part_mask, void* const outs[3], int32_t dtype,
-                              hipStream_t st, int32_t* taken);   // gemm_pp.hip
-
-// K >= 768 with N % 256 == 0 (the ViT-B linears) run on the persistent 256 x 256 kernel of gemm_pp.hip.  Residual linears with
-// 768 output columns take it from K = 3072 on (fc2: the LayerNorm behind it then runs as its own launch instead of in the
-// whole-row kernel's epilogue: 1.56 against 1.87 ms per 64 slices); proj, K = 768, stays on the whole-row kernel.
-static bool use_pp_residual(int k) { return k >= 3072; }
-
+// Dispatch of a linear, in this order: the whole-row kernel (residual epilogue, rows_first, vittf_gemm_rows_covers), the
+// persistent 256 x 256 kernel (vittf_gemm_pp_covers + vittf_gemm_pp_covers_out: K >= 768 with N % 256 == 0, the ViT-B
+// linears), the 128 x 128 tiles of this file.  The predicates are the only place a kernel's coverage is written down.
 extern "C" int vittf_gemm(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n,
                           int32_t k, int32_t epilogue, int32_t tokens, int32_t dtype, void* stream) {
   if (!a || !w || !bias || !out || rows <= 0 || n <= 0 || k <= 0) return VITTF_ERR_INVALID_ARG;
   if (n % BN != 0 || k % BK != 0) return VITTF_ERR_INVALID_ARG;
+  if (epilogue < VITTF_EPI_BIAS || epilogue > VITTF_EPI_BIAS_QKV) return VITTF_ERR_INVALID_ARG;
   if (epilogue == VITTF_EPI_KFEAT && tokens < 2) return VITTF_ERR_INVALID_ARG;
   if (rows / BM + 1 > (1 << 20)) return VITTF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  // residual epilogue with 384 / 768 output columns (ViT-S / ViT-B proj and fc2): whole-row kernel
-  const bool pp_first = use_pp_residual(k) && n == 768 && k >= 768;
-  if (!pp_first && epilogue == VITTF_EPI_BIAS_RESIDUAL && (n == 384 || n == 768)) {
-    const int rc = vittf_gemm_rows(a, w, bias, (float*)out, rows, n, k, dtype, nullptr, nullptr, 0.f, nullptr, st);
-    if (rc != 1) return rc;
-  }
-  {
-    const int rc = vittf_gemm_pp(a, w, bias, out, rows, n, k, epilogue, tokens, dtype, st);
-    if (rc != 1) return rc;
+  if (epilogue == VITTF_EPI_BIAS_RESIDUAL && rows_first(n, k) && vittf_gemm_rows_covers(n, k, rows))
+    return vittf_gemm_rows(a, w, bias, (float*)out, rows, n, k, dtype, nullptr, nullptr, 0.f, nullptr, st);
+  const int64_t kfeat_bytes = epilogue == VITTF_EPI_KFEAT ? vittf_kfeat_out_bytes(rows, n, tokens, 1) : 0;
+  if (vittf_gemm_pp_covers(k, n, a, w) && vittf_gemm_pp_covers_out(out, kfeat_bytes))
+    return vittf_gemm_pp(a, w, bias, out, rows, n, k, epilogue, tokens, dtype, st);
+  if (epilogue == VITTF_EPI_KFEAT) {   // one slot: the [n][k] weights as third 0 of width n, the CLS row dropped
+    void* const outs[3] = {out, nullptr, nullptr};
+    return launch_gemm_kfeat(a, w, bias, rows, n, k, tokens, 1, 1, n, outs, dtype, st);
   }
   if (dtype == VITTF_BF16) return launch_gemm<VITTF_BF16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
   if (dtype == VITTF_FP16) return launch_gemm<VITTF_FP16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
@@ -315,19 +330,8 @@ extern "C" int vittf_gemm_kfeat_parts_reg(const void* a, const void* w, const fl
   if (rc != VITTF_OK) return rc;
   const int rest = part_mask & ~taken;
   if (!rest) return VITTF_OK;
-  KfeatParts kp{};
-  int slots = 0;
-  for (int p = 0; p < 3; ++p) {
-    kp.out[p] = (unsigned short*)outs[p];
-    if ((rest >> p) & 1) kp.part[slots++] = p;
-  }
-  kp.d = d;
-  kp.drop = 1 + n_reg;
-  const int part_tiles = slots * (d / BN);
   vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_kernel");   // (the projection is the engine's last launch: its class name tells which ran)
-  if (dtype == VITTF_BF16)
-    return launch_gemm<VITTF_BF16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
-  return launch_gemm<VITTF_FP16>(a, w, bias, nullptr, rows, 3 * d, k, EPI_KFEAT_PARTS, tokens, st, kp, part_tiles);
+  return launch_gemm_kfeat(a, w, bias, rows, d, k, tokens, 1 + n_reg, rest, 3 * d, outs, dtype, st);
 }
 
 extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
@@ -338,18 +342,14 @@ extern "C" int vittf_gemm_kfeat_parts(const void* a, const void* w, const float*
 
 // x += a . w^T + bias (fp32 residual stream, n = 384), then h = LayerNorm(x; g, b) as the 16-bit operand of the next
 // GEMM: whole-row kernel with the LayerNorm in its epilogue; shapes it does not cover take the two separate kernels.
-extern "C" int vittf_layernorm(const float* x, const float* g, const float* b, void* y, int64_t rows, int32_t d, float eps,
-                               int32_t dtype, void* stream);
 extern "C" int vittf_gemm_residual_ln(const void* a, const void* w, const float* bias, float* x, int64_t rows, int32_t n,
                                       int32_t k, int32_t dtype, const float* ln_g, const float* ln_b, float ln_eps, void* h,
                                       void* stream) {
   if (!a || !w || !bias || !x || !ln_g || !ln_b || !h || rows <= 0 || n <= 0 || k <= 0) return VITTF_ERR_INVALID_ARG;
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if ((n == 384 || n == 768) && !(use_pp_residual(k) && n == 768 && k >= 768)) {
-    const int rc = vittf_gemm_rows(a, w, bias, x, rows, n, k, dtype, ln_g, ln_b, ln_eps, h, st);
-    if (rc != 1) return rc;
-  }
+  if (rows_first(n, k) && vittf_gemm_rows_covers(n, k, rows))
+    return vittf_gemm_rows(a, w, bias, x, rows, n, k, dtype, ln_g, ln_b, ln_eps, h, st);
   const int rc = vittf_gemm(a, w, bias, x, rows, n, k, VITTF_EPI_BIAS_RESIDUAL, 0, dtype, stream);
   if (rc != VITTF_OK) return rc;
   return vittf_layernorm(x, ln_g, ln_b, h, rows, n, ln_eps, dtype, stream);

@@ -27,7 +27,10 @@
 //     stages are already in the ring.  The counted waits of a tile's first two stages know how many stores lie in between.
 //   * a partial last row tile reads zeros for its missing rows (descriptor bounds) and drops their outputs: a row's bits do
 //     not depend on where it sits in a launch.
-#include "vittf_common.h"
+//   * what the kernel covers (shape, alignment, output size) is written once, in vittf_gemm_pp_covers / _covers_out below:
+//     every caller asks them in front of the launch, and the launchers refuse what they do not cover.
+//   * one K-feature epilogue (PP_EPI_KFEAT_PARTS): vittf_gemm_pp(VITTF_EPI_KFEAT) is its one-slot launch.
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 
@@ -75,9 +78,11 @@ __device__ __forceinline__ int pp_scale_exp(float amax) {
   return ex < -20 ? -20 : ex;
 }
 
-// Several thirds of attn.qkv in one launch with the K-feature epilogue (entry point vittf_gemm_pp_kfeat_parts below; internal
-// epilogue id): W / bias are the whole projection, the grid covers the column tiles of the requested thirds only (slot s =
-// third part[s]), and each third leaves through a descriptor of its own over its own output (64-bit base, `bytes` long).
+// The K-feature epilogue (the hooked tensor: fp16 values, the leading rows of every slice dropped), for several thirds of
+// attn.qkv in one launch (entry point vittf_gemm_pp_kfeat_parts below; internal epilogue id): W / bias are the whole
+// projection, the grid covers the column tiles of the requested thirds only (slot s = third part[s]), and each third leaves
+// through a descriptor of its own over its own output (64-bit base, `bytes` long).  vittf_gemm_pp(VITTF_EPI_KFEAT) is the
+// same launch with one slot: its [n][k] weights as third 0 of width d = n, drop = 1.
 // Dropped rows (CLS and the register rows behind it, rows past the end) are predicated off, not sent to an out-of-range offset; the tile's stores are then
 // fewer than the counted waits of the next tile's first stages assume, so this epilogue ends on a full vmcnt(0).
 constexpr int PP_EPI_KFEAT_PARTS = 101;
@@ -95,7 +100,7 @@ template <int DT, int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* __restrict__ A, const unsigned short* __restrict__ W,
                                                          const float* __restrict__ bias, void* __restrict__ out, int64_t rows,
                                                          int n, int k, int tokens, int n_tiles, int total_tiles,
-                                                         unsigned out_bytes, PpFp8Out f8, PpParts kp) {
+                                                         PpFp8Out f8, PpParts kp) {
   __shared__ __attribute__((aligned(16))) char smem[PLDS];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -283,12 +288,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
       const int64_t left = rows - row0;
       const int vr = left <= 0 ? 0 : left < 32 ? (int)left : 32;
       constexpr int ES = RES ? 4 : 2;
-      // (K features: CLS rows dropped, the others move up -- infer.py:202 k[:, 1:] --: per-lane output row, one descriptor
-      //  over the whole output, 32-bit byte offsets checked by the launcher, dropped rows get an offset outside it)
-      const auto rs = EPI == VITTF_EPI_KFEAT
-          ? __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out), 0, (int)out_bytes, 0x00020000)
-          : __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out) + (vr ? (row0 * n + n0) * ES : 0), 0,
-                                              vr ? ((vr - 1) * n + PBN) * ES : 0, 0x00020000);
+      const auto rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(out) + (vr ? (row0 * n + n0) * ES : 0), 0,
+                                                        vr ? ((vr - 1) * n + PBN) * ES : 0, 0x00020000);
       [[maybe_unused]] pu32x4_t xv[4];
       if constexpr (RES) {
 #pragma unroll
@@ -398,19 +399,10 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
             const int64_t m = row0 + rl;
             const int64_t b = m / tokens;
             const int tok = (int)(m - b * tokens);
-            const int64_t orow = b * (tokens - kp.drop) + tok - kp.drop;
+            const int64_t orow = b * (tokens - kp.drop) + tok - kp.drop;      // (infer.py:202 k[:, 1:]: the kept rows move up)
             if (m < rows && tok >= kp.drop)  // (byte offset < bytes <= 0xfffffff0: checked by the launcher)
               __builtin_amdgcn_raw_buffer_store_b128(pk, rp, (int)(unsigned)((orow * kp.d + (n0 - third * kp.d) + 4 * ch) * 2),
                                                      0, PP_STORE_AUX);
-          } else if constexpr (EPI == VITTF_EPI_KFEAT) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<VITTF_FP16>(v[2 * e], v[2 * e + 1]);
-            const int64_t m = row0 + rl;
-            const int64_t b = m / tokens;
-            const int tok = (int)(m - b * tokens);
-            const int64_t orow = b * (tokens - 1) + tok - 1;
-            const unsigned off = (m < rows && tok != 0) ? (unsigned)((orow * n + n0 + 4 * ch) * 2) : 0x80000000u;      // (dropped rows: an offset whose 16 bytes cannot wrap into the buffer)
-            __builtin_amdgcn_raw_buffer_store_b128(pk, rs, (int)off, 0, PP_STORE_AUX);
           } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) pk[e] = pack2_h16<DT>(v[2 * e], v[2 * e + 1]);
@@ -454,24 +446,17 @@ int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_
   if (cus <= 0) return VITTF_ERR_NO_DEVICE;
   // persistent: one workgroup per CU; the stride between a workgroup's tiles must keep it on its XCD (xcd_remap)
   const int grid = total < cus ? total : (cus & ~7) ? (cus & ~7) : cus;
-  unsigned out_bytes = 0;
-  if (epi == VITTF_EPI_KFEAT) {
-    const int64_t ob = (rows - rows / tokens) * (int64_t)n * 2;
-    if (ob > 0xfffffff0ll) return 1;             // (32-bit byte offsets in that epilogue: the caller's other kernel takes it)
-    out_bytes = (unsigned)ob;
-  }
   const unsigned short* A = (const unsigned short*)a;
   const unsigned short* Wp = (const unsigned short*)w;
 #define VITTF_PP_CASE(E)                                                                                              \
   case E:                                                                                                             \
     hipLaunchKernelGGL((gemm_pp_kernel<DT, E>), dim3(grid), dim3(512), 0, st, A, Wp, bias, out, rows, n, k, tokens,   \
-                       n_tiles, total, out_bytes, f8, kp);                                                            \
+                       n_tiles, total, f8, kp);                                                                       \
     break;
   switch (epi) {
     VITTF_PP_CASE(VITTF_EPI_BIAS)
     VITTF_PP_CASE(VITTF_EPI_BIAS_GELU)
     VITTF_PP_CASE(VITTF_EPI_BIAS_RESIDUAL)
-    VITTF_PP_CASE(VITTF_EPI_KFEAT)
     VITTF_PP_CASE(VITTF_EPI_BIAS_QKV)
     VITTF_PP_CASE(PP_EPI_QKV_FP8)
     VITTF_PP_CASE(PP_EPI_KFEAT_PARTS)
@@ -483,35 +468,49 @@ int launch_pp(const void* a, const void* w, const float* bias, void* out, int64_
 
 }  // namespace
 
-// 1 = shape not covered (the caller falls back to gemm.hip's 128 x 128 tiles)
-int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
-                  int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st) {
-  if (k < 768 || k % (2 * PBK) != 0 || n % PBN != 0) return 1;
-  if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)n * 4 * 64 > 0x7fffffff) return 1;      // per-lane offsets are 32-bit
-  if ((((uintptr_t)a | (uintptr_t)w | (uintptr_t)out) & 15) != 0) return 1;
-  vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_pp_kernel");
-  if (dtype == VITTF_BF16) return launch_pp<VITTF_BF16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
-  if (dtype == VITTF_FP16) return launch_pp<VITTF_FP16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
-  return VITTF_ERR_INVALID_ARG;
+// What this kernel covers, asked by every caller in front of the launch (the dispatch of gemm.hip falls back to its 128 x 128
+// tiles): the shape -- `columns` = the output columns, of ONE third for the K-feature thirds -- with 16-byte aligned operands ...
+bool vittf_gemm_pp_covers(int32_t k, int32_t columns, const void* a, const void* w) {
+  if (k < 768 || k % (2 * PBK) != 0 || columns % PBN != 0) return false;
+  if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)columns * 4 * 64 > 0x7fffffff) return false;   // per-lane offsets are 32-bit
+  return (((uintptr_t)a | (uintptr_t)w) & 15) == 0;
 }
 
-// vittf_gemm_kfeat_parts' persistent leg: the thirds of part_mask whose single-third vittf_gemm(EPI_KFEAT) call would run here
-// (same shape, alignment and output-size rules as vittf_gemm_pp + launch_pp; on [3 d][k] weights, a third's are 16-byte
-// aligned when the whole are) in one launch.  *taken = the thirds launched; the others are the caller's.
+// ... and the output: 16-byte aligned; a K-feature output (kfeat_bytes = vittf_kfeat_out_bytes, else 0) is addressed by 32-bit
+// byte offsets inside one buffer descriptor
+bool vittf_gemm_pp_covers_out(const void* out, int64_t kfeat_bytes) {
+  return ((uintptr_t)out & 15) == 0 && kfeat_bytes <= 0xfffffff0ll;
+}
+
+int vittf_gemm_pp(const void* a, const void* w, const float* bias, void* out, int64_t rows, int32_t n, int32_t k,
+                  int32_t epilogue, int32_t tokens, int32_t dtype, hipStream_t st) {
+  if (epilogue < VITTF_EPI_BIAS || epilogue > VITTF_EPI_BIAS_QKV) return VITTF_ERR_INVALID_ARG;
+  if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
+  if (epilogue == VITTF_EPI_KFEAT) {   // one slot: the [n][k] weights as third 0 of width n, the CLS row dropped
+    void* const outs[3] = {out, nullptr, nullptr};
+    int32_t taken = 0;
+    const int rc = vittf_gemm_pp_kfeat_parts(a, w, bias, rows, n, k, tokens, 0, 1, outs, dtype, st, &taken);
+    return rc != VITTF_OK || taken == 1 ? rc : VITTF_ERR_INVALID_ARG;
+  }
+  if (!vittf_gemm_pp_covers(k, n, a, w) || !vittf_gemm_pp_covers_out(out, 0)) return VITTF_ERR_INVALID_ARG;
+  vittf_note_kernel(VITTF_KERNEL_GEMM, "gemm_pp_kernel");
+  if (dtype == VITTF_BF16) return launch_pp<VITTF_BF16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
+  return launch_pp<VITTF_FP16>(a, w, bias, out, rows, n, k, epilogue, tokens, st);
+}
+
+// vittf_gemm_kfeat_parts' persistent leg: the thirds of part_mask that this kernel covers (on [3 d][k] weights, a third's are
+// 16-byte aligned when the whole are) in one launch.  *taken = the thirds launched; the others are the caller's.
 int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, int64_t rows, int32_t d, int32_t k,
                               int32_t tokens, int32_t n_reg, int32_t part_mask, void* const outs[3], int32_t dtype,
                               hipStream_t st, int32_t* taken) {
   *taken = 0;
-  if (k < 768 || k % (2 * PBK) != 0 || d % PBN != 0) return VITTF_OK;
-  if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)d * 4 * 64 > 0x7fffffff) return VITTF_OK;
-  if ((((uintptr_t)a | (uintptr_t)w) & 15) != 0) return VITTF_OK;
-  const int64_t ob = (rows - rows / tokens * (1 + n_reg)) * (int64_t)d * 2;     // (whole slices: the engine's case)
-  if (ob > 0xfffffff0ll) return VITTF_OK;
+  if (!vittf_gemm_pp_covers(k, d, a, w)) return VITTF_OK;
+  const int64_t ob = vittf_kfeat_out_bytes(rows, d, tokens, 1 + n_reg);     // (whole slices: the engine's case)
   PpParts kp{};
   int slots = 0, mask = 0;
   for (int p = 0; p < 3; ++p) {
     kp.out[p] = (char*)outs[p];
-    if (((part_mask >> p) & 1) && ((uintptr_t)outs[p] & 15) == 0) { kp.part[slots++] = p; mask |= 1 << p; }
+    if (((part_mask >> p) & 1) && vittf_gemm_pp_covers_out(outs[p], ob)) { kp.part[slots++] = p; mask |= 1 << p; }
   }
   if (!mask) return VITTF_OK;
   kp.d = d;
@@ -525,9 +524,6 @@ int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, i
   if (rc == VITTF_OK) *taken = mask;
   return rc;
 }
-
-void vittf_fp8_ws_pointers(void* ws, int32_t batch, int32_t tokens, int32_t heads, unsigned** amax, unsigned char** q8,
-                           unsigned char** k8, unsigned char** qs, unsigned char** ks, int32_t* np);   // attention_fp8.hip
 
 // Attention.qkv with fp8 outputs for vittf_attention_fp8_rows: see include/vittf.h
 // The last 64-row tile of every (slice, head) of q8 / k8 and of their scale bytes, zeroed in front of the GEMM that fills its valid
@@ -551,10 +547,10 @@ extern "C" int vittf_gemm_qkv_fp8(const void* a, const void* w, const float* bia
                                   int32_t k, int32_t tokens, int32_t heads, int32_t dtype, void* ws, size_t ws_bytes,
                                   void* stream) {
   if (!a || !w || !bias || !qkv_out || !ws || rows <= 0 || tokens <= 0 || heads <= 0) return VITTF_ERR_INVALID_ARG;
-  if (n != 3 * heads * 64 || (n / 3) % PBN != 0 || k < 768 || k % (2 * PBK) != 0) return VITTF_ERR_INVALID_ARG;
+  if (n != 3 * heads * 64 || (n / 3) % PBN != 0) return VITTF_ERR_INVALID_ARG;      // (a column tile lies inside one third)
   if (rows % tokens != 0 || rows / tokens > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
-  if ((int64_t)k * 2 * PBM > 0x7fffffff || (int64_t)n * 4 * 64 > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
-  if ((((uintptr_t)a | (uintptr_t)w | (uintptr_t)qkv_out) & 15) != 0 || ((uintptr_t)ws & 255) != 0) return VITTF_ERR_INVALID_ARG;
+  if (!vittf_gemm_pp_covers(k, n, a, w) || !vittf_gemm_pp_covers_out(qkv_out, 0)) return VITTF_ERR_INVALID_ARG;
+  if (((uintptr_t)ws & 255) != 0) return VITTF_ERR_INVALID_ARG;
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   const int batch = (int)(rows / tokens);
   if (ws_bytes < vittf_attention_fp8_workspace_bytes(batch, tokens, heads)) return VITTF_ERR_WORKSPACE;

@@ -26,7 +26,7 @@
 //     where it sits in a launch (1 rank and N ranks batch the slices differently and must write the same file).
 //   * where the time goes, measured with timing-only builds: fc2 + LayerNorm 0.235 ms without MFMAs, 0.19 ms without the
 //     epilogue, 0.30 ms complete.
-#include "vittf_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 
@@ -254,11 +254,15 @@ __global__ __launch_bounds__((RowsCfg<WM, RN>::THREADS)) __attribute__((amdgpu_w
 
 }  // namespace
 
-// 1 = shape not covered
+// the shapes this kernel covers (whether it is asked first: the dispatch's rows_first, gemm.hip)
+bool vittf_gemm_rows_covers(int32_t n, int32_t k, int64_t rows) {
+  if ((n != 384 && n != 768) || k % RBK != 0 || k < 2 * RBK || rows <= 0) return false;
+  return (int64_t)256 * k * 2 <= 0x7fffffff && rows / 128 + 1 <= 0x7fffffff;      // 32-bit per-lane offsets, grid
+}
+
 int vittf_gemm_rows(const void* a, const void* w, const float* bias, float* x, int64_t rows, int32_t n, int32_t k,
                     int32_t dtype, const float* ln_g, const float* ln_b, float ln_eps, void* h, hipStream_t st) {
-  if ((n != 384 && n != 768) || k % RBK != 0 || k < 2 * RBK || rows <= 0) return 1;
-  if ((int64_t)256 * k * 2 > 0x7fffffff || rows / 128 + 1 > 0x7fffffff) return 1;
+  if (!vittf_gemm_rows_covers(n, k, rows)) return VITTF_ERR_INVALID_ARG;
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   // Workgroup shape by K (never by the row count: results must not depend on how the rows are batched): the 256-row
   // shape for the long-K linear (fc2: 239 against 254 ms per 3072 slices), the 128-row one for proj (123 against 127).

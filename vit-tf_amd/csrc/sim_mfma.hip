@@ -23,7 +23,7 @@
 //     feeds four MFMAs instead of two, and every staged chunk serves twice the voxels -- the 5 x 1024-query preset was bound
 //     by exactly these two streams) or ONE block of 768 features (ViT-B/8 volumes: a 32-query chunk is two units, the
 //     accumulators run over both before the activation).
-#include "vittf_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 #include <vector>

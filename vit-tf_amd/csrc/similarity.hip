@@ -8,7 +8,7 @@
 // regime (A <= a few dozen) the dot products are HBM-bound: every voxel's 2*F bytes are read ONCE per chunk of 16
 // annotations, coalesced 4 B per lane, and the reference's A*4 B/voxel intermediate never exists.  Query vectors
 // are wave-uniform (scalar loads of a transposed [F][16] copy); all arithmetic is fp32 like the reference CPU path.
-#include "vittf_common.h"
+#include "vittf_internal.h"
 
 #include <stdlib.h>
 
@@ -525,15 +525,6 @@ extern "C" int vittf_voxel_norm(const uint16_t* feat, int32_t f, int64_t nvox, f
                      out);
   return vittf_check_launch();
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t vittf_sim_mfma_workspace_bytes(int32_t classes, int32_t annotations);                      // sim_mfma.hip
-bool vittf_sim_mfma_applies(int32_t f, int32_t classes, int32_t total_a, const void* ws, size_t ws_bytes, const void* feat,
-                            int64_t nvox);
-int vittf_sim_mfma_maps(const unsigned short* feat, int32_t f, int64_t nvox, const float* qf, const int32_t* class_start_host,
-                        int32_t classes, const float* voxel_norm, float* sim, unsigned* maxbits, void* ws, size_t ws_bytes,
-                        hipStream_t st);                                                         // 1 = not applicable
 
 namespace {
 struct SimWs { size_t maxbits, qf_t, mfma, mfma_bytes, maps, total; };
