@@ -202,7 +202,7 @@ int vittf_vit_features(const vittf_vit_config* cfg, const vittf_vit_weights* w, 
                        int32_t n_reg, const vittf_rope_table* table, const float* norm_g, const float* norm_b, uint16_t* q_out,
                        uint16_t* k_out, uint16_t* v_out, uint16_t* t_out, void* ws, size_t ws_bytes, void* stream);
 
-/* Optional timing of the launches inside vittf_vit_k_features and vittf_similarity, by kernel class, with HIP events recorded on
+/* Optional timing of the launches inside vittf_vit_features (and the entry points that forward to it) and vittf_similarity, by kernel class, with HIP events recorded on
  * the caller's stream (what bench.py's roofline leg reads).  Process-global, off by default, not thread-safe:
  * the one exception to "no global mutable state".  enable(mask) clears earlier records and starts recording the
  * classes whose bit (1 << vittf_kernel_class) is set (-1: all; two event records per launch cost ~2-3 % of the

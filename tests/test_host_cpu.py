@@ -344,6 +344,37 @@ def test_gemm_kernels_have_one_kfeat_epilogue(tmp_path):
             assert int(re.search(r'ScratchSize \[bytes/lane\]: (\d+)', l).group(1)) <= scratch.get(e, 0), l
 
 
+def test_attention_kernels_register_contract(tmp_path):
+    """The attention kernels share their frame (csrc/attn_common.h, csrc/fp8_rows.h) and keep their schedules, each laid out for
+    a number of waves per SIMD: attn_kernel 4, attn_pp64_kernel 2 (at the register limit), attn_fp8_kernel 3 with and without
+    row scales; scratch per lane at most what they had when the frame was shared (100 / 12 / 0 / 0 bytes), the quantise kernel
+    -- one template with and without the q / k thirds -- none.  Every instantiation in bf16 and fp16.  Read from the
+    resource-usage remarks alone."""
+    import re
+    import shutil
+    if not shutil.which('/opt/rocm/bin/hipcc'):
+        pytest.skip('no hipcc')
+    both = (_lib.BF16, _lib.FP16)
+    # source -> kernel -> {template arguments behind the dtype: (least waves per SIMD, most scratch bytes per lane)}
+    for src, kernels in (('attention.hip', {'attn_kernel': {(): (4, 100)}}),
+                         ('attention_pp64.hip', {'attn_pp64_kernel': {(): (2, 12)}}),
+                         ('attention_fp8.hip', {'attn_fp8_kernel': {(0,): (3, 0), (1,): (3, 0)},
+                                                'quant_kernel': {(0,): (1, 0), (1,): (1, 0)}})):
+        r = _kernel_asm(src, tmp_path)
+        assert r.returncode == 0, r.stdout + r.stderr
+        for kern, contract in kernels.items():
+            usage = {}
+            for l in r.stdout.splitlines():
+                m = re.search(r'\d+%sILi(\d+)E(?:Lb(\d)E)?E' % kern, l)
+                if m and 'ScratchSize' in l:
+                    usage[(int(m.group(1)),) + ((int(m.group(2)),) if m.group(2) else ())] = l
+            assert sorted(usage) == sorted((dt,) + args for dt in both for args in contract), (kern, sorted(usage))
+            for key, l in usage.items():
+                occupancy, scratch = contract[key[1:]]
+                assert int(re.search(r'Occupancy \[waves/SIMD\]: (\d+)', l).group(1)) >= occupancy, l
+                assert int(re.search(r'ScratchSize \[bytes/lane\]: (\d+)', l).group(1)) <= scratch, l
+
+
 def test_window_goldens_cover_the_fullsize_tests():
     """tests/golden/windows512.npz (made by tests/golden/make_window_goldens.py from the CPU oracle) holds every pooled window the
     full-size GPU tests compare with: fp16, every 4th feature row / column of a (D, 64, 64) window, finite, not constant."""

@@ -35,6 +35,7 @@
 // blocks run along the KEYS: they cross the rows a GEMM tile produces); its absmax comes from that GEMM's epilogue and only
 // the v third goes through the quantise + re-lay kernel (vittf_attention_fp8_rows).
 #include "attn_common.h"
+#include "fp8_rows.h"
 #include "vittf_internal.h"
 
 namespace {
@@ -42,7 +43,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
 constexpr int QT = 128;      // query rows per workgroup
-constexpr int KT = 64;       // keys per tile
+constexpr int KT = FP8_KT;   // keys per tile
 constexpr int TILE_B = KT * 64;            // one fp8 operand tile: 4 KB
 constexpr int BUF_B = 2 * TILE_B;          // K | V^T
 // P is stored as fp8(2 p), p = exp2(s - M) with M such that the row maximum of the tile that set it is 1.  The overflow
@@ -53,27 +54,6 @@ constexpr int BUF_B = 2 * TILE_B;          // K | V^T
 constexpr float P_HEADROOM = 2.f;
 constexpr int P_HEADROOM_LOG2 = 1;
 constexpr float P_SUM_BOUND = 256.f;
-
-// power-of-two scale exponent for a tensor with absolute maximum amax: amax * 2^-e <= 448 (e4m3 maximum), e >= -20
-__device__ __forceinline__ int scale_exp(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int ex;
-  (void)frexpf(amax * (1.0f / 448.0f), &ex);        // amax / 448 = m 2^ex, m in [0.5, 1)
-  return ex < -20 ? -20 : ex;
-}
-
-__device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
-}
-
-// slot of key `kin` (0..63) inside its tile of V8T: inverse of key = 32 b + (r & 3) + 8 (r >> 2) + 4 h, slot = 32 h + 16 b + r
-__device__ __forceinline__ int vt_slot(int kin) {
-  const int b = kin >> 5, w = kin & 31;
-  const int h = (w >> 2) & 1, r = (w & 3) + 4 * (w >> 3);
-  return 32 * h + 16 * b + r;
-}
 
 // ---------------------------------------------------------------- 1. absmax per (slice, head, q|k|v)
 template <int DT>
@@ -111,7 +91,9 @@ __global__ __launch_bounds__(256) void absmax_kernel(const unsigned short* __res
 }
 
 // ---------------------------------------------------------------- 2. quantise + re-lay (one 64-token tile of one head)
-template <int DT>
+// QK: all three thirds (q8 / k8 as natural rows with the (slice, head) scale); else the v third alone -- q and k arrive as
+// fp8 from the GEMM (vittf_attention_fp8_rows) and q8 / k8 are not touched
+template <int DT, bool QK>
 __global__ __launch_bounds__(256) void quant_kernel(const unsigned short* __restrict__ qkv, int tokens, int heads, int np,
                                                     const unsigned* __restrict__ amax_bits, unsigned char* __restrict__ q8,
                                                     unsigned char* __restrict__ k8, unsigned char* __restrict__ v8t) {
@@ -121,68 +103,35 @@ __global__ __launch_bounds__(256) void quant_kernel(const unsigned short* __rest
   const int dmodel = heads * 64, ld = 3 * dmodel;
   const int tile = blockIdx.x, kin = tid >> 2, quarter = tid & 3;
   const int tok = tile * 64 + kin;
-  float inv[3];
-#pragma unroll
-  for (int p = 0; p < 3; ++p) inv[p] = ldexpf(1.0f, -scale_exp(__uint_as_float(amax_bits[bh * 3 + p])));
+  constexpr int P0 = QK ? 0 : 2;                                           // first third handled
   unsigned w[3][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-  if (tok < tokens) {
-    const unsigned short* row = qkv + ((int64_t)b * tokens + tok) * ld + hd * 64 + 16 * quarter;
+  const unsigned short* row = qkv + ((int64_t)b * tokens + tok) * ld + hd * 64 + 16 * quarter;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+  for (int p = P0; p < 3; ++p) {
+    const float inv = ldexpf(1.0f, -scale_exp(__uint_as_float(amax_bits[bh * 3 + p])));
+    if (tok < tokens) {
       const s16x8_t v0 = *reinterpret_cast<const s16x8_t*>(row + p * dmodel);
       const s16x8_t v1 = *reinterpret_cast<const s16x8_t*>(row + p * dmodel + 8);
       float f[16];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        f[j] = h16_to_f32<DT>((unsigned short)v0[j]) * inv[p];
-        f[8 + j] = h16_to_f32<DT>((unsigned short)v1[j]) * inv[p];
+        f[j] = h16_to_f32<DT>((unsigned short)v0[j]) * inv;
+        f[8 + j] = h16_to_f32<DT>((unsigned short)v1[j]) * inv;
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) w[p][j] = pack4_fp8(f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3]);
     }
   }
-  // q, k: natural [token][64] rows (rows >= tokens are written as zeros: the key padding of the last tile)
-  const int64_t rowoff = ((int64_t)bh * np + tok) * 64 + 16 * quarter;
-  *reinterpret_cast<uint4*>(q8 + rowoff) = make_uint4(w[0][0], w[0][1], w[0][2], w[0][3]);
-  *reinterpret_cast<uint4*>(k8 + rowoff) = make_uint4(w[1][0], w[1][1], w[1][2], w[1][3]);
+  if constexpr (QK) {
+    // q, k: natural [token][64] rows (rows >= tokens are written as zeros: the key padding of the last tile)
+    const int64_t rowoff = fp8_row_index(bh, np, tok) * 64 + 16 * quarter;
+    *reinterpret_cast<uint4*>(q8 + rowoff) = make_uint4(w[0][0], w[0][1], w[0][2], w[0][3]);
+    *reinterpret_cast<uint4*>(k8 + rowoff) = make_uint4(w[1][0], w[1][1], w[1][2], w[1][3]);
+  }
   // v: through LDS into [dim][slot]
   const int slot = vt_slot(kin);
 #pragma unroll
   for (int j = 0; j < 16; ++j) vt[16 * quarter + j][slot] = (unsigned char)(w[2][j >> 2] >> (8 * (j & 3)));
-  __syncthreads();
-  const int d = tid >> 2;
-  const uint4 o = *reinterpret_cast<const uint4*>(&vt[d][16 * quarter]);
-  *reinterpret_cast<uint4*>(v8t + ((int64_t)bh * 64 + d) * np + tile * 64 + 16 * quarter) = o;
-}
-
-// ---------------------------------------------------------------- 2b. the v third alone (q / k arrive as fp8 from the GEMM)
-template <int DT>
-__global__ __launch_bounds__(256) void quant_v_kernel(const unsigned short* __restrict__ qkv, int tokens, int heads, int np,
-                                                      const unsigned* __restrict__ amax_bits, unsigned char* __restrict__ v8t) {
-  __shared__ __attribute__((aligned(16))) unsigned char vt[64][64 + 16];   // [dim][slot], padded rows
-  const int bh = blockIdx.y, b = bh / heads, hd = bh % heads;
-  const int tid = threadIdx.x;
-  const int dmodel = heads * 64, ld = 3 * dmodel;
-  const int tile = blockIdx.x, kin = tid >> 2, quarter = tid & 3;
-  const int tok = tile * 64 + kin;
-  const float inv = ldexpf(1.0f, -scale_exp(__uint_as_float(amax_bits[bh * 3 + 2])));
-  unsigned w[4] = {0u, 0u, 0u, 0u};
-  if (tok < tokens) {
-    const unsigned short* row = qkv + ((int64_t)b * tokens + tok) * ld + 2 * dmodel + hd * 64 + 16 * quarter;
-    const s16x8_t v0 = *reinterpret_cast<const s16x8_t*>(row);
-    const s16x8_t v1 = *reinterpret_cast<const s16x8_t*>(row + 8);
-    float f[16];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      f[j] = h16_to_f32<DT>((unsigned short)v0[j]) * inv;
-      f[8 + j] = h16_to_f32<DT>((unsigned short)v1[j]) * inv;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = pack4_fp8(f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3]);
-  }
-  const int slot = vt_slot(kin);
-#pragma unroll
-  for (int j = 0; j < 16; ++j) vt[16 * quarter + j][slot] = (unsigned char)(w[j >> 2] >> (8 * (j & 3)));
   __syncthreads();
   const int d = tid >> 2;
   const uint4 o = *reinterpret_cast<const uint4*>(&vt[d][16 * quarter]);
@@ -224,9 +173,8 @@ __global__ __launch_bounds__(256, 3) void attn_fp8_kernel(const unsigned char* _
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF_B];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, l31 = lane & 31;
-  const int item = xcd_remap(blockIdx.x, total);
-  const int qt = item % q_tiles, bh = item / q_tiles;
-  const int hd = bh % heads, b = bh / heads;
+  const AttnItem w = attn_item(q_tiles, heads, total);
+  const int qt = w.qt, bh = w.bh, hd = w.hd, b = w.b;
   const int dmodel = heads * 64;
 
   const int eq = ROWSC ? 0 : scale_exp(__uint_as_float(amax_bits[bh * 3 + 0]));
@@ -239,14 +187,14 @@ __global__ __launch_bounds__(256, 3) void attn_fp8_kernel(const unsigned char* _
   // Q fragment (B operand): lane holds Q[row l31][32 hh .. +31]
   const int qrow = qt * QT + wave * 32 + l31;
   const int qrow_c = qrow < tokens ? qrow : tokens - 1;
-  if constexpr (ROWSC) sc_q = scale_operand((int)qs[((int64_t)bh * np + qrow_c) * 2 + hh]);      // this lane's row and block
+  if constexpr (ROWSC) sc_q = scale_operand((int)qs[fp8_row_index(bh, np, qrow_c) * 2 + hh]);      // this lane's row and block
   // K scales: lane (l31, hh) of key block bk needs the byte of key 64 t + 32 bk + l31, block hh
-  const unsigned char* ksl = ROWSC ? ks + ((int64_t)bh * np + l31) * 2 + hh : nullptr;
+  const unsigned char* ksl = ROWSC ? ks + fp8_row_index(bh, np, l31) * 2 + hh : nullptr;
   int ksc[2] = {sc_k, sc_k};
   if constexpr (ROWSC) { ksc[0] = scale_operand((int)ksl[0]); ksc[1] = scale_operand((int)ksl[64]); }
   i32x8_t qf;
   {
-    const unsigned char* qp = q8 + ((int64_t)bh * np + qrow_c) * 64 + 32 * hh;
+    const unsigned char* qp = q8 + fp8_row_index(bh, np, qrow_c) * 64 + 32 * hh;
     const uint4 lo = *reinterpret_cast<const uint4*>(qp), hi = *reinterpret_cast<const uint4*>(qp + 16);
     qf[0] = (int)lo.x; qf[1] = (int)lo.y; qf[2] = (int)lo.z; qf[3] = (int)lo.w;
     qf[4] = (int)hi.x; qf[5] = (int)hi.y; qf[6] = (int)hi.z; qf[7] = (int)hi.w;
@@ -254,7 +202,7 @@ __global__ __launch_bounds__(256, 3) void attn_fp8_kernel(const unsigned char* _
 
   // staging: LDS position p = tid (16-byte chunk index 0..255) of each operand image <- row p >> 2, source chunk
   const int srow = tid >> 2, schunk = (tid & 3) ^ ((srow >> 2) & 3);
-  const unsigned char* ksrc = k8 + (int64_t)bh * np * 64 + srow * 64 + 16 * schunk;             // + t * 4096
+  const unsigned char* ksrc = k8 + fp8_row_index(bh, np, srow) * 64 + 16 * schunk;             // + t * 4096
   const unsigned char* vsrc = v8t + ((int64_t)bh * 64 + srow) * np + 16 * schunk;               // + t * 64
   const unsigned dma_dst = (unsigned)(size_t)LDS_PTR(smem) + (__builtin_amdgcn_readfirstlane(tid & ~63) << 4);
   auto stage = [&](int t, int buf) {
@@ -294,13 +242,7 @@ __global__ __launch_bounds__(256, 3) void attn_fp8_kernel(const unsigned char* _
         const i32x8_t kf = read_frag(kt, 32 * bk + l31, hh);
         s[bk] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf, qf, negm, 0, 0, 0, ksc[bk], 0, sc_q);
       }
-      if (t == nt - 1) {
-#pragma unroll
-        for (int bk = 0; bk < 2; ++bk)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            if (t * KT + 32 * bk + acc_row(r, hh) >= tokens) s[bk][r] = -INFINITY;
-      }
+      if (t == nt - 1) { mask_keys(s[0], t * KT, tokens, hh); mask_keys(s[1], t * KT + 32, tokens, hh); }
       float p[2][16];
       float ps = 0.f;
 #pragma unroll
@@ -353,111 +295,55 @@ __global__ __launch_bounds__(256, 3) void attn_fp8_kernel(const unsigned char* _
 
   // normalise (l carries the head-room factor, O does not) and store: lane owns query row qrow,
   // columns 32 dvt + 8 g + 4 hh + {0..3}
-  float l_tot;
-  {
-    const unsigned lb = __float_as_uint(l_run);
-    const auto sw = __builtin_amdgcn_permlane32_swap(lb, lb, false, false);
-    l_tot = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-  }
-  const float inv = P_HEADROOM / l_tot;
+  const float inv = row_sum_inv(l_run, P_HEADROOM);
   if (qrow < tokens) store_o_row<DT>(out + ((int64_t)b * tokens + qrow) * dmodel + hd * 64, hh, o0, o1, inv);
 }
 
-struct Fp8Ws { size_t amax, q8, k8, v8t, qs, ks, total; int np; };
-Fp8Ws fp8_ws(int batch, int tokens, int heads) {
-  Fp8Ws w;
-  w.np = (tokens + KT - 1) / KT * KT;
-  const size_t per = (size_t)batch * heads * w.np * 64;
-  const size_t sc = ((size_t)batch * heads * w.np * 2 + 255) & ~(size_t)255;     // row scales (vittf_gemm_qkv_fp8)
-  w.amax = 0;
-  w.q8 = ((size_t)batch * heads * 3 * 4 + 255) & ~(size_t)255;
-  w.k8 = w.q8 + per;
-  w.v8t = w.k8 + per;
-  w.qs = w.v8t + per;
-  w.ks = w.qs + sc;
-  w.total = w.ks + sc;
-  return w;
-}
-
-}  // namespace
-
-extern "C" size_t vittf_attention_fp8_workspace_bytes(int32_t batch, int32_t tokens, int32_t heads) {
-  if (batch <= 0 || tokens <= 0 || heads <= 0) return 0;
-  return fp8_ws(batch, tokens, heads).total;
-}
-
-extern "C" int vittf_attention_fp8(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
-                                   void* ws, size_t ws_bytes, void* stream) {
-  vittf_note_kernel(VITTF_KERNEL_ATTENTION, "attn_fp8_kernel (+ absmax + quantise)");
+// The launches of both entry points: validation, the carving of the workspace, and (ROWS) q8 / k8 with their row scales
+// already there from vittf_gemm_qkv_fp8 -- only the v third is quantised -- or (!ROWS) absmax + all three thirds
+template <bool ROWS>
+int launch_fp8(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype, void* ws, size_t ws_bytes,
+               hipStream_t st) {
   if (!qkv || !out || !ws || batch <= 0 || tokens <= 0 || heads <= 0) return VITTF_ERR_INVALID_ARG;
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)ws & 255) != 0) return VITTF_ERR_INVALID_ARG;
-  const Fp8Ws w = fp8_ws(batch, tokens, heads);
+  const Fp8Ws w = fp8_ws(ws, batch, tokens, heads);
   if (ws_bytes < w.total) return VITTF_ERR_WORKSPACE;
   if ((int64_t)batch * heads > 65535) return VITTF_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)ws;
-  unsigned* amax = (unsigned*)(base + w.amax);
-  unsigned char* q8 = (unsigned char*)(base + w.q8);
-  unsigned char* k8 = (unsigned char*)(base + w.k8);
-  unsigned char* v8t = (unsigned char*)(base + w.v8t);
-  if (hipMemsetAsync(amax, 0, (size_t)batch * heads * 3 * 4, st) != hipSuccess) return VITTF_ERR_LAUNCH;
-  const int tiles = w.np / KT;
-  const dim3 grid(tiles, batch * heads);
+  if (!ROWS && hipMemsetAsync(w.amax, 0, (size_t)batch * heads * 3 * 4, st) != hipSuccess) return VITTF_ERR_LAUNCH;
+  const dim3 grid(w.np / KT, batch * heads);
   const int q_tiles = (tokens + QT - 1) / QT;
   const int total = batch * heads * q_tiles;
-#define FP8_LAUNCH(DTV)                                                                                                 \
-  {                                                                                                                     \
-    hipLaunchKernelGGL((absmax_kernel<DTV>), grid, dim3(256), 0, st, (const unsigned short*)qkv, tokens, heads, amax);  \
-    hipLaunchKernelGGL((quant_kernel<DTV>), grid, dim3(256), 0, st, (const unsigned short*)qkv, tokens, heads, w.np,    \
-                       amax, q8, k8, v8t);                                                                              \
-    hipLaunchKernelGGL((attn_fp8_kernel<DTV, false>), dim3(total), dim3(256), 0, st, q8, k8, v8t, amax,                 \
-                       (unsigned short*)out, tokens, heads, w.np, q_tiles, total, (const unsigned char*)nullptr,        \
-                       (const unsigned char*)nullptr);                                                                  \
+#define FP8_LAUNCH(DTV)                                                                                                  \
+  {                                                                                                                      \
+    if (!ROWS) hipLaunchKernelGGL((absmax_kernel<DTV>), grid, dim3(256), 0, st, (const unsigned short*)qkv, tokens,      \
+                                  heads, w.amax);                                                                        \
+    hipLaunchKernelGGL((quant_kernel<DTV, !ROWS>), grid, dim3(256), 0, st, (const unsigned short*)qkv, tokens, heads,    \
+                       w.np, w.amax, w.q8, w.k8, w.v8t);                                                                 \
+    hipLaunchKernelGGL((attn_fp8_kernel<DTV, ROWS>), dim3(total), dim3(256), 0, st, w.q8, w.k8, w.v8t, w.amax,           \
+                       (unsigned short*)out, tokens, heads, w.np, q_tiles, total, ROWS ? w.qs : nullptr,                 \
+                       ROWS ? w.ks : nullptr);                                                                           \
   }
   if (dtype == VITTF_BF16) FP8_LAUNCH(VITTF_BF16) else FP8_LAUNCH(VITTF_FP16)
 #undef FP8_LAUNCH
   return vittf_check_launch();
 }
 
-// Where vittf_gemm_qkv_fp8 (gemm_pp.hip) puts its outputs inside the workspace of this file (C++ linkage, not part of the ABI).
-void vittf_fp8_ws_pointers(void* ws, int32_t batch, int32_t tokens, int32_t heads, unsigned** amax, unsigned char** q8,
-                           unsigned char** k8, unsigned char** qs, unsigned char** ks, int32_t* np) {
-  const Fp8Ws w = fp8_ws(batch, tokens, heads);
-  char* base = (char*)ws;
-  *amax = (unsigned*)(base + w.amax); *q8 = (unsigned char*)(base + w.q8); *k8 = (unsigned char*)(base + w.k8);
-  *qs = (unsigned char*)(base + w.qs); *ks = (unsigned char*)(base + w.ks); *np = w.np;
+}  // namespace
+
+extern "C" size_t vittf_attention_fp8_workspace_bytes(int32_t batch, int32_t tokens, int32_t heads) {
+  if (batch <= 0 || tokens <= 0 || heads <= 0) return 0;
+  return fp8_ws(nullptr, batch, tokens, heads).total;
+}
+
+extern "C" int vittf_attention_fp8(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  vittf_note_kernel(VITTF_KERNEL_ATTENTION, "attn_fp8_kernel (+ absmax + quantise)");
+  return launch_fp8<false>(qkv, out, batch, tokens, heads, dtype, ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int vittf_attention_fp8_rows(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
                                         void* ws, size_t ws_bytes, void* stream) {
   vittf_note_kernel(VITTF_KERNEL_ATTENTION, "attn_fp8_kernel<row scales> (+ quantise v)");
-  if (!qkv || !out || !ws || batch <= 0 || tokens <= 0 || heads <= 0) return VITTF_ERR_INVALID_ARG;
-  if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
-  if (((uintptr_t)ws & 255) != 0) return VITTF_ERR_INVALID_ARG;
-  const Fp8Ws w = fp8_ws(batch, tokens, heads);
-  if (ws_bytes < w.total) return VITTF_ERR_WORKSPACE;
-  if ((int64_t)batch * heads > 65535) return VITTF_ERR_INVALID_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  char* base = (char*)ws;
-  const unsigned* amax = (const unsigned*)(base + w.amax);
-  const unsigned char* q8 = (const unsigned char*)(base + w.q8);
-  const unsigned char* k8 = (const unsigned char*)(base + w.k8);
-  unsigned char* v8t = (unsigned char*)(base + w.v8t);
-  const unsigned char* qs = (const unsigned char*)(base + w.qs);
-  const unsigned char* ks = (const unsigned char*)(base + w.ks);
-  const int tiles = w.np / KT;
-  const dim3 grid(tiles, batch * heads);
-  const int q_tiles = (tokens + QT - 1) / QT;
-  const int total = batch * heads * q_tiles;
-#define FP8R_LAUNCH(DTV)                                                                                                \
-  {                                                                                                                     \
-    hipLaunchKernelGGL((quant_v_kernel<DTV>), grid, dim3(256), 0, st, (const unsigned short*)qkv, tokens, heads, w.np,  \
-                       amax, v8t);                                                                                      \
-    hipLaunchKernelGGL((attn_fp8_kernel<DTV, true>), dim3(total), dim3(256), 0, st, q8, k8, v8t, amax,                  \
-                       (unsigned short*)out, tokens, heads, w.np, q_tiles, total, qs, ks);                              \
-  }
-  if (dtype == VITTF_BF16) FP8R_LAUNCH(VITTF_BF16) else FP8R_LAUNCH(VITTF_FP16)
-#undef FP8R_LAUNCH
-  return vittf_check_launch();
+  return launch_fp8<true>(qkv, out, batch, tokens, heads, dtype, ws, ws_bytes, (hipStream_t)stream);
 }

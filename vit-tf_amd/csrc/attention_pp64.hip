@@ -2,8 +2,8 @@
 // ("ping-pong"), two waves per SIMD.  Same contract as attention.hip (softmax(q k^T / 8) v per head; Attention.forward of
 // the upstream model the reference calls, infer.py:177), same LDS images, same lazy running maximum.
 //
-// What a 32-rows-per-wave kernel (round 2's software-pipelined attention_pipe.hip, 0.40 of peak) pays per MFMA besides the softmax arithmetic is operand
-// delivery and synchronisation: 12 LDS fragment instructions, half a barrier and 2 LDS-DMA issues per 8 MFMAs.  Here every
+// What a 32-rows-per-wave kernel (round 2's software-pipelined one, removed in round 3: 0.40 of peak) pays per MFMA besides the
+// softmax arithmetic is operand delivery and synchronisation: 12 LDS fragment instructions, half a barrier and 2 LDS-DMA issues per 8 MFMAs.  Here every
 // K / V^T fragment feeds the MFMAs of both blocks of the wave, and a 64-key tile serves 256 query rows of the workgroup:
 // all three halve.  The software pipeline needs no second score tile either -- the two blocks ARE the two stages:
 //
@@ -34,40 +34,17 @@ constexpr int KT = ATT_KT;               // keys per tile
 constexpr int KVB = ATT_KV_TILE_BYTES;   // bytes per operand and tile
 constexpr int BUFB = ATT_BUF_BYTES;      // K | V
 
-struct LdsBases { const char *ka0, *ka1, *ka2, *ka3, *va0, *va1; };
 struct KFrag { s16x8_t k[4]; };          // K rows (A operand of S^T = K Q^T), one per 16-wide d chunk
 struct VFrag { s16x8_t v[4]; };          // V^T (A operand of O^T = V^T P^T): [2 x key step s2 + d half dvt]
-struct QFrag { s16x8_t q[4]; };          // Q rows (B operand), resident
 struct Blk {                             // running state of one 32-row query block
   f32x16_t o0, o1, negm;
   float l_run;
 };
 
-__device__ __forceinline__ s16x8_t ld_k(const LdsBases& b, int i, int off) {
-  const char* base = i == 0 ? b.ka0 : i == 1 ? b.ka1 : i == 2 ? b.ka2 : b.ka3;
-  return *reinterpret_cast<const s16x8_t*>(base + off);
-}
-__device__ __forceinline__ s16x8_t ld_v(const LdsBases& b, int j, int off) {
-  const int imm = off + 2048 * (j >> 1) + 512 * (j & 1);
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(b.va0 + imm));
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(b.va1 + imm + 1024));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 template <int DT> __device__ __forceinline__ f32x16_t score_mfma(const KFrag& k, const QFrag& q, f32x16_t c) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) c = mfma32<DT>(k.k[i], q.q[i], c);
   return c;
-}
-
-__device__ __forceinline__ float tile_max(const f32x16_t& s) {
-  float tmax = max3_f32(s[0], s[1], s[2]);
-#pragma unroll
-  for (int r = 3; r < 15; r += 2) tmax = max3_f32(tmax, s[r], s[r + 1]);
-  tmax = fmaxf(tmax, s[15]);
-  const unsigned tb = __float_as_uint(tmax);
-  const auto sw = __builtin_amdgcn_permlane32_swap(tb, tb, false, false);
-  return max3_f32(tmax, __uint_as_float(sw[0]), __uint_as_float(sw[1]));      // both lane halves agree
 }
 
 // executions of the overflow branch (statistics, vittf_attention_rescale_count): one relaxed atomic per execution, on a
@@ -90,12 +67,8 @@ __device__ __forceinline__ float rescale_block(const LdsBases& b, Blk& X, const 
 #pragma unroll
   for (int i = 0; i < 4; ++i) kh.k[i] = ld_k(b, i, ck_off);
   raw = score_mfma<DT>(kh, qX, raw);
-  if (mask) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (key0 + acc_row(r, h) >= tokens) raw[r] = -INFINITY;
-  }
-  const float tmax = tile_max(raw);
+  if (mask) mask_keys(raw, key0, tokens, h);
+  const float tmax = tile_max(raw, -INFINITY);
   const float delta = fmaxf(tmax + X.negm[0], 0.f);                       // M moves up by delta (per query column)
   const float alpha = __builtin_amdgcn_exp2f(-delta);
   X.l_run *= alpha;
@@ -121,6 +94,25 @@ __device__ __forceinline__ float rescale_block(const LdsBases& b, Blk& X, const 
   return psum0 + psum1;
 }
 
+// One unit of a phase's softmax arithmetic: two of block X's 16 scores -> exp2, the two row-sum chains, one conversion
+template <int DT>
+__device__ __forceinline__ void softmax_unit(const f32x16_t& sX, int g, float& psum0, float& psum1, u32x4_t& pk0, u32x4_t& pk1) {
+  const float e0 = __builtin_amdgcn_exp2f(sX[2 * g]);
+  const float e1 = __builtin_amdgcn_exp2f(sX[2 * g + 1]);
+  if (g == 0) { psum0 = e0; psum1 = e1; } else { psum0 += e0; psum1 += e1; }
+  const unsigned w = pack2_h16<DT>(e0, e1);
+  if (g < 4) pk0[g] = w; else pk1[g - 4] = w;
+}
+// The end of a phase: P of block X handed over, the overflow check on its row sum (-> rescale_block), the row sum booked
+template <int DT>
+__device__ __forceinline__ void phase_end(const LdsBases& b, Blk& X, const QFrag& qX, s16x8_t (&pX)[2], float ps, u32x4_t pk0,
+                                          u32x4_t pk1, int ck_off, bool mask, int key0, int tokens, int h) {
+  pX[0] = __builtin_bit_cast(s16x8_t, pk0);
+  pX[1] = __builtin_bit_cast(s16x8_t, pk1);
+  if (__builtin_expect(__any(!(ps <= p_limit<DT>())), 0)) ps = rescale_block<DT>(b, X, qX, pX, ck_off, mask, key0, tokens, h);
+  X.l_run += ps;
+}
+
 // One phase of the steady state (see the header): softmax of block X's score tile sX (consumed) -> packed P in pX, beside
 // 4 + 4 MFMAs for the OTHER block Y -- S_Y = kf Q_Y^T - M_Y into sY, O_Y += vf^T pY^T -- and, with LOAD, the refill of each
 // fragment register right behind the MFMA that read it last (K from byte offset nk_off, V^T from nv_off).  Eight gaps,
@@ -132,11 +124,7 @@ template <int DT, bool LOAD, bool MASK>
 __device__ __forceinline__ void pp_phase(const LdsBases& b, Blk& X, const QFrag& qX, f32x16_t& sX, s16x8_t (&pX)[2], Blk& Y,
                                          const QFrag& qY, f32x16_t& sY, const s16x8_t (&pY)[2], KFrag& kf, VFrag& vf, int ck_off,
                                          int nk_off, int nv_off, int key0, int tokens, int h) {
-  if constexpr (MASK) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (key0 + acc_row(r, h) >= tokens) sX[r] = -INFINITY;
-  }
+  if constexpr (MASK) mask_keys(sX, key0, tokens, h);
   float psum0 = 0.f, psum1 = 0.f;
   u32x4_t pk0, pk1;
 #pragma unroll
@@ -150,18 +138,10 @@ __device__ __forceinline__ void pp_phase(const LdsBases& b, Blk& X, const QFrag&
       else       Y.o0 = mfma32<DT>(vf.v[i], pY[i >> 1], Y.o0);
       if constexpr (LOAD) vf.v[i] = ld_v(b, i, nv_off);
     }
-    const float e0 = __builtin_amdgcn_exp2f(sX[2 * g]);
-    const float e1 = __builtin_amdgcn_exp2f(sX[2 * g + 1]);
-    if (g == 0) { psum0 = e0; psum1 = e1; } else { psum0 += e0; psum1 += e1; }
-    const unsigned w = pack2_h16<DT>(e0, e1);
-    if (g < 4) pk0[g] = w; else pk1[g - 4] = w;
+    softmax_unit<DT>(sX, g, psum0, psum1, pk0, pk1);
     __builtin_amdgcn_sched_barrier(0);
   }
-  float ps = psum0 + psum1;
-  pX[0] = __builtin_bit_cast(s16x8_t, pk0);
-  pX[1] = __builtin_bit_cast(s16x8_t, pk1);
-  if (__builtin_expect(__any(!(ps <= p_limit<DT>())), 0)) ps = rescale_block<DT>(b, X, qX, pX, ck_off, MASK, key0, tokens, h);
-  X.l_run += ps;
+  phase_end<DT>(b, X, qX, pX, psum0 + psum1, pk0, pk1, ck_off, MASK, key0, tokens, h);
 }
 
 // The same phase with RUN-TIME ring offsets and flags, for the tiles outside the steady-state loop (the first tile, the up to
@@ -188,27 +168,12 @@ __device__ __forceinline__ void pp_phase_rt(const LdsBases& b, Blk& X, const QFr
 #pragma unroll
     for (int j = 0; j < 4; ++j) vf.v[j] = ld_v(b, j, nv_off);
   }
-  if (mask) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      if (key0 + acc_row(r, h) >= tokens) sX[r] = -INFINITY;
-  }
+  if (mask) mask_keys(sX, key0, tokens, h);
   float psum0 = 0.f, psum1 = 0.f;
   u32x4_t pk0, pk1;
 #pragma unroll
-  for (int g = 0; g < 8; ++g) {
-    const float e0 = __builtin_amdgcn_exp2f(sX[2 * g]);
-    const float e1 = __builtin_amdgcn_exp2f(sX[2 * g + 1]);
-    psum0 += e0;
-    psum1 += e1;
-    const unsigned w = pack2_h16<DT>(e0, e1);
-    if (g < 4) pk0[g] = w; else pk1[g - 4] = w;
-  }
-  float ps = psum0 + psum1;
-  pX[0] = __builtin_bit_cast(s16x8_t, pk0);
-  pX[1] = __builtin_bit_cast(s16x8_t, pk1);
-  if (__builtin_expect(__any(!(ps <= p_limit<DT>())), 0)) ps = rescale_block<DT>(b, X, qX, pX, ck_off, mask, key0, tokens, h);
-  X.l_run += ps;
+  for (int g = 0; g < 8; ++g) softmax_unit<DT>(sX, g, psum0, psum1, pk0, pk1);
+  phase_end<DT>(b, X, qX, pX, psum0 + psum1, pk0, pk1, ck_off, mask, key0, tokens, h);
 }
 
 template <int DT>
@@ -219,89 +184,28 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(const unsigned short*
   const int lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
 
-  const int item = xcd_remap(blockIdx.x, total);
-  const int qt = item % q_tiles;
-  const int bh = item / q_tiles;
-  const int hd = bh % heads, bi = bh / heads;
+  const AttnItem w = attn_item(q_tiles, heads, total);
   const int dmodel = heads * 64;
   const int ld = 3 * dmodel;                                   // elements per token row of qkv
-  const unsigned short* base = qkv + (int64_t)bi * tokens * ld;
+  const QkvSlice sl = qkv_slice(qkv, w.b, tokens, ld);
 
-  // buffer descriptor over this slice's qkv rows: loads past the last token return 0
-  const i32x4_t rsrc = lds_dma_rsrc(base, (unsigned)((int64_t)tokens * ld * 2));
+  // block b of the wave = rows + 32
+  const int qrow_a = w.qt * QT + wave * 64 + l31, qrow_b = qrow_a + 32;
+  QFrag qa = load_q(sl.base, qrow_a, tokens, ld, w.hd, h), qb = load_q(sl.base, qrow_b, tokens, ld, w.hd, h);
 
-  // ---- Q fragments (B operand): lane holds Q[row][16 s + 8 h .. +7]; block b of the wave = rows + 32 ----
-  QFrag qa, qb;
-  const int qrow_a = qt * QT + wave * 64 + l31, qrow_b = qrow_a + 32;
-  {
-    const unsigned short* pa_ = base + (int64_t)(qrow_a < tokens ? qrow_a : tokens - 1) * ld + hd * 64 + 8 * h;
-    const unsigned short* pb_ = base + (int64_t)(qrow_b < tokens ? qrow_b : tokens - 1) * ld + hd * 64 + 8 * h;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      qa.q[i] = *reinterpret_cast<const s16x8_t*>(pa_ + 16 * i);
-      qb.q[i] = *reinterpret_cast<const s16x8_t*>(pb_ + 16 * i);
-    }
-  }
-
-  // ---- LDS-DMA staging: which (row, chunk) each lane fetches so that the lane-linear destination is the image.
-  //      Piece i of a wave covers linear 16-byte positions [i * 256 + tid, ...) of an operand image. ----
-  //      The second piece of an operand is the first one 32 rows further on (tile_pos / v_pos of position + 256: the same
-  //      chunk of row + 32), so one voffset per operand serves both and the 32-row step rides in the scalar offset.
-  int voff_k, voff_v;
-  {
-    int r, cc, key, ch;
-    tile_pos(tid, r, cc);
-    voff_k = (r * ld + dmodel + hd * 64 + cc * 8) * 2;
-    v_pos(tid, key, ch);
-    voff_v = (key * ld + 2 * dmodel + hd * 64 + ch * 8) * 2;
-  }
-  const int tile_stride = KT * ld * 2, half_stride = 32 * ld * 2;
+  const KvStage stg = kv_stage(tid, ld, dmodel, w.hd);
   const int nt = (tokens + KT - 1) / KT;
   const unsigned dma_dst = (unsigned)(size_t)LDS_PTR(smem) + (__builtin_amdgcn_readfirstlane(tid & ~63) << 4);
-  // the last tile carries its offset in the range-checked voffset (see attention.hip)
-#define PP_STAGE_TILE(t_, bufi_)                                                                    \
-  {                                                                                                 \
-    const int so_ = (t_) * tile_stride;                                                             \
-    const unsigned dst_ = dma_dst + (bufi_) * BUFB;                                                 \
-    if ((t_) == nt - 1) {                                                                           \
-      int vk_ = voff_k, vv_ = voff_v;   /* opaque copies: the sums below are formed here, not kept alive through the loop */ \
-      asm volatile("" : "+v"(vk_), "+v"(vv_));                                                      \
-      _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                            \
-        lds_dma16(rsrc, dst_ + i_ * 4096, vk_ + so_ + i_ * half_stride, 0);                         \
-        lds_dma16(rsrc, dst_ + KVB + i_ * 4096, vv_ + so_ + i_ * half_stride, 0);                   \
-      }                                                                                             \
-    } else {                                                                                        \
-      _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                            \
-        lds_dma16(rsrc, dst_ + i_ * 4096, voff_k, so_ + i_ * half_stride);                          \
-        lds_dma16(rsrc, dst_ + KVB + i_ * 4096, voff_v, so_ + i_ * half_stride);                    \
-      }                                                                                             \
-    }                                                                                               \
-  }
+  auto stage = [&](int t, int buf) { stage_tile(sl.rsrc, stg, dma_dst + buf * BUFB, t, nt); };
 
-  // ---- per-lane LDS read bases (tile_off / v_off: buffer, half, s2, dvt, jj terms are immediates) ----
-  LdsBases b;
-  {
-    const int p_l = l31 >> 1;
-    const int bslot = (((l31 & 1) << 3) | h) ^ (p_l & 15);
-    b.ka0 = smem + (p_l << 8) + ((bslot ^ 0) << 4);
-    b.ka1 = smem + (p_l << 8) + ((bslot ^ 2) << 4);
-    b.ka2 = smem + (p_l << 8) + ((bslot ^ 4) << 4);
-    b.ka3 = smem + (p_l << 8) + ((bslot ^ 6) << 4);
-    const int g16 = lane >> 4;
-    const int tr_q = (lane & 15) >> 2;
-    const int tr_p = lane & 3;
-    const int tr_ch = 2 * (g16 & 1) + (tr_p >> 1);
-    const int vl0 = 64 * (4 * h + tr_q) + 16 * (tr_ch ^ h) + 8 * (tr_p & 1);
-    b.va0 = smem + vl0;
-    b.va1 = smem + (vl0 ^ 32);
-  }
+  const LdsBases b = lds_bases(smem, lane);
 
   // ---- prologue: tiles 0 and 1 land and are published together; tile 2 leaves right behind the barrier ----
-  PP_STAGE_TILE(0, 0)
-  if (nt > 1) PP_STAGE_TILE(1, 1)
+  stage(0, 0);
+  if (nt > 1) stage(1, 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (nt > 2) PP_STAGE_TILE(2, 2)
+  if (nt > 2) stage(2, 2);
   // Q loads retired here, not re-waited inside the loop
   asm volatile("" : "+v"(qa.q[0]), "+v"(qa.q[1]), "+v"(qa.q[2]), "+v"(qa.q[3]), "+v"(qb.q[0]), "+v"(qb.q[1]), "+v"(qb.q[2]), "+v"(qb.q[3]));
 
@@ -311,10 +215,10 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(const unsigned short*
   {                                                                                                 \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                \
     __syncthreads();                                                                                \
-    if (t + 2 < nt) PP_STAGE_TILE(t + 2, BNEXT2)                                                    \
+    if (t + 2 < nt) stage(t + 2, BNEXT2);                                                           \
   }
 
-  const bool active = __builtin_amdgcn_readfirstlane(qt * QT + wave * 64) < tokens;
+  const bool active = __builtin_amdgcn_readfirstlane(w.qt * QT + wave * 64) < tokens;
   if (!active) {   // all rows past the end: keep staging and synchronising, skip the arithmetic
     for (int t = 1; t < nt; ++t) {
       const int b2 = (t + 2) % NBUF;
@@ -338,12 +242,8 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(const unsigned short*
     for (int i = 0; i < 4; ++i) kf.k[i] = ld_k(b, i, 0);
     sa = score_mfma<DT>(kf, qa, A.negm);
     sb = score_mfma<DT>(kf, qb, B.negm);
-    if (nt == 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        if (acc_row(r, h) >= tokens) { sa[r] = -INFINITY; sb[r] = -INFINITY; }
-    }
-    const float ta = tile_max(sa), tb = tile_max(sb);
+    if (nt == 1) { mask_keys(sa, 0, tokens, h); mask_keys(sb, 0, tokens, h); }
+    const float ta = tile_max(sa, -INFINITY), tb = tile_max(sb, -INFINITY);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { A.negm[r] = -ta; sa[r] -= ta; B.negm[r] = -tb; sb[r] -= tb; }
   }
@@ -393,7 +293,6 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(const unsigned short*
 #undef PP_COLD_TILE
 #undef PP_TILE
 #undef PP_TILE_BARRIER
-#undef PP_STAGE_TILE
   // block b's output product of the very last half step (its V^T fragments were fetched by the last A phase)
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -404,10 +303,8 @@ __global__ __launch_bounds__(256, 2) void attn_pp64_kernel(const unsigned short*
   // ---- normalise and store: lane owns query rows qrow_a / qrow_b, columns 32 dvt + 8 g + 4 h + {0..3}
   //      (store_o_row pairs them into 16-byte runs) ----
   auto store = [&](const Blk& X, int qrow) {
-    const unsigned lb = __float_as_uint(X.l_run);
-    const auto sw = __builtin_amdgcn_permlane32_swap(lb, lb, false, false);
-    const float inv = 1.0f / (__uint_as_float(sw[0]) + __uint_as_float(sw[1]));
-    if (qrow < tokens) store_o_row<DT>(out + ((int64_t)bi * tokens + qrow) * dmodel + hd * 64, h, X.o0, X.o1, inv);
+    const float inv = row_sum_inv(X.l_run);
+    if (qrow < tokens) store_o_row<DT>(out + ((int64_t)w.b * tokens + qrow) * dmodel + w.hd * 64, h, X.o0, X.o1, inv);
   };
   store(A, qrow_a);
   store(B, qrow_b);

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, 4) void gemm_kernel(const unsigned short* __re
           }
           if constexpr (EPI == VITTF_EPI_BIAS_QKV) {
             // the q third carries the softmax scale and the exp -> exp2 base change: one rounding, like plain q
-            const float sc = (n0 + nl) < n / 3 ? 0.125f * 1.44269504088896340736f : 1.0f;
+            const float sc = (n0 + nl) < n / 3 ? VITTF_Q_PRESCALE : 1.0f;
             v0 *= sc; v1 *= sc; v2 *= sc; v3 *= sc;
           }
           uint2 pk;

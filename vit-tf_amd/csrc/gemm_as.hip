@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512, 1) void gemm_as_kernel(const unsigned short* _
   const unsigned stg_rp = lds0 + STG_OFF + 2 * (wave & 3) * STG + q8 * STG_ROW + c8 * 16;      // (storer) its partner's buffers
   unsigned cl = lds0 + BIAS_OFF + 16 * h;
   asm volatile("" : "+v"(cl));
-  constexpr float QS = 0.125f * 1.44269504088896340736f;   // log2(e) / 8 on the q third (the attention kernels work in exp2)
+  constexpr float QS = VITTF_Q_PRESCALE;   // on the q third
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   s16x8_t wf[NF];

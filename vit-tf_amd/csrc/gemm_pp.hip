@@ -30,6 +30,7 @@
 //   * what the kernel covers (shape, alignment, output size) is written once, in vittf_gemm_pp_covers / _covers_out below:
 //     every caller asks them in front of the launch, and the launchers refuse what they do not cover.
 //   * one K-feature epilogue (PP_EPI_KFEAT_PARTS): vittf_gemm_pp(VITTF_EPI_KFEAT) is its one-slot launch.
+#include "fp8_rows.h"
 #include "vittf_internal.h"
 
 #include <stdlib.h>
@@ -59,8 +60,7 @@ __device__ __forceinline__ int p_img_off(int r, int kc) { return tile_off(r >> 1
 typedef __attribute__((ext_vector_type(4))) unsigned pu32x4_t;
 
 // The qkv projection with q and k leaving as fp8 (e4m3) rows with MX block scales -- one power-of-two (E8M0 byte) per row and
-// 32-wide block -- in the layout attention_fp8.hip reads ([slice][head][token][64] bytes in the instruction's block order,
-// [slice][head][token][2] scale bytes),
+// 32-wide block -- in the layout attention_fp8.hip reads (fp8_rows.h),
 // v as 16-bit values in `out` (the qkv buffer's v third) with its per-(slice, head) absolute maximum collected on the way
 // (internal epilogue id; entry point vittf_gemm_qkv_fp8 below).
 constexpr int PP_EPI_QKV_FP8 = 100;
@@ -68,15 +68,6 @@ struct PpFp8Out {
   unsigned char* q8; unsigned char* k8; unsigned char* qs; unsigned char* ks; unsigned* amax;
   int np, heads, batch;
 };
-
-// power-of-two scale exponent for a block with absolute maximum amax: amax * 2^-e <= 448 (e4m3 maximum), e >= -20
-// (the rule of attention_fp8.hip's scale_exp)
-__device__ __forceinline__ int pp_scale_exp(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int ex;
-  (void)frexpf(amax * (1.0f / 448.0f), &ex);
-  return ex < -20 ? -20 : ex;
-}
 
 // The K-feature epilogue (the hooked tensor: fp16 values, the leading rows of every slice dropped), for several thirds of
 // attn.qkv in one launch (entry point vittf_gemm_pp_kfeat_parts below; internal epilogue id): W / bias are the whole
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
     // residual: a thread owns 4 columns (one staged chunk) of 4 rows; 16-bit outputs: 8 columns (two chunks -> one 16-byte
     // store: the epilogue is bound by the NUMBER of store instructions) of 2 rows
     const int ch = RES ? (tid & 63) : 2 * (tid & 31);
-    [[maybe_unused]] const float qs = (n0 + 4 * ch) < n / 3 ? 0.125f * 1.44269504088896340736f : 1.0f;   // (uniform per tile when 256 | n / 3)
+    [[maybe_unused]] const float qs = (n0 + 4 * ch) < n / 3 ? VITTF_Q_PRESCALE : 1.0f;   // (uniform per tile when 256 | n / 3)
     [[maybe_unused]] float vmax_a = 0.f, vmax_b = 0.f;     // (fp8 qkv epilogue, v tiles) this thread's maxima: first / second slice of the tile
     [[maybe_unused]] int64_t fb0 = 0;
     if constexpr (EPI == PP_EPI_QKV_FP8) fb0 = m0 / tokens;
@@ -333,22 +324,15 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(const unsigned short* _
         if (third < 2) {
           // this row's 32-wide block = the 16 + 16 columns of two neighbouring lanes: block maximum -> E8M0 scale -> e4m3 bytes
           mx = fmaxf(mx, __shfl_xor(mx, 1));
-          const int ex = pp_scale_exp(mx);
+          const int ex = scale_exp(mx);
           const float inv = ldexpf(1.0f, -ex);
           pu32x4_t pk8;
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * inv, v[4 * j + 1] * inv, 0, false);
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * inv, v[4 * j + 3] * inv, w0, true);
-            pk8[j] = (unsigned)w0;
-          }
+          for (int j = 0; j < 4; ++j) pk8[j] = pack4_fp8(v[4 * j] * inv, v[4 * j + 1] * inv, v[4 * j + 2] * inv, v[4 * j + 3] * inv);
           const int col = (n0 - third * dm) + 16 * c16;                   // column inside the third: head 64 * hd + dim
           const int hd = col >> 6, dim = col & 63;
-          // position of dim inside the 64-byte row: the matrix instruction's MX block b of a row is bytes 16 b .. 16 b + 15 of
-          // BOTH lane halves (k = 32 (byte >> 4) + 16 (lane >> 5) + (byte & 15): tools/micro/mfma_f8_scale_probe2), and the
-          // attention kernel's lane half hh reads bytes 32 hh .. 32 hh + 31: a row is stored as [d 0-15 | d 32-47 | d 16-31 | d 48-63]
-          const int pos = ((dim >> 4) & 1) * 32 + (dim >> 5) * 16;
-          const int64_t rowi = (b * f8.heads + hd) * f8.np + tok;
+          const int pos = fp8_row_pos(dim);
+          const int64_t rowi = fp8_row_index(b * f8.heads + hd, f8.np, tok);
           const bool ok = m < rows;
           const int64_t total8 = (int64_t)f8.batch * f8.heads * f8.np;
           const auto r8 = __builtin_amdgcn_make_buffer_rsrc(third == 0 ? f8.q8 : f8.k8, 0, (int)(unsigned)(total8 * 64), 0x00020000);
@@ -553,11 +537,10 @@ extern "C" int vittf_gemm_qkv_fp8(const void* a, const void* w, const float* bia
   if (((uintptr_t)ws & 255) != 0) return VITTF_ERR_INVALID_ARG;
   if (dtype != VITTF_BF16 && dtype != VITTF_FP16) return VITTF_ERR_INVALID_ARG;
   const int batch = (int)(rows / tokens);
-  if (ws_bytes < vittf_attention_fp8_workspace_bytes(batch, tokens, heads)) return VITTF_ERR_WORKSPACE;
-  PpFp8Out f8;
-  int np = 0;
-  vittf_fp8_ws_pointers(ws, batch, tokens, heads, &f8.amax, &f8.q8, &f8.k8, &f8.qs, &f8.ks, &np);
-  f8.np = np; f8.heads = heads; f8.batch = batch;
+  const Fp8Ws fw = fp8_ws(ws, batch, tokens, heads);
+  if (ws_bytes < fw.total) return VITTF_ERR_WORKSPACE;
+  const int np = fw.np;
+  const PpFp8Out f8 = {fw.q8, fw.k8, fw.qs, fw.ks, fw.amax, np, heads, batch};
   if ((int64_t)batch * heads * np * 64 > 0xfffffff0ll) return VITTF_ERR_INVALID_ARG;       // 32-bit byte offsets into q8 / k8
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(f8.amax, 0, (size_t)batch * heads * 3 * 4, st) != hipSuccess) return VITTF_ERR_LAUNCH;

@@ -45,6 +45,12 @@ template <int DT> __device__ __forceinline__ unsigned pack2_h16(float lo, float 
   else return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
 }
 
+// The q pre-scale: softmax scale 1 / sqrt(64) times log2(e), the exp -> exp2 base change.  Producer: the q third of the
+// VITTF_EPI_BIAS_QKV epilogues (gemm.hip, gemm_as.hip, gemm_pp.hip -- its fp8 qkv epilogue too).  Consumer: the attention
+// kernels on pre-scaled q (attention_pp64.hip, attention_fp8.hip), which take exp2 of the scores as they arrive;
+// attention.hip applies the same factor itself when q is not pre-scaled.
+constexpr float VITTF_Q_PRESCALE = 0.125f * 1.44269504088896340736f;
+
 // ---- MFMA 32x32x16, fp32 accumulate.  Lane l: A[row l&31][k 8(l>>5)+j], B[k 8(l>>5)+j][col l&31];
 //      C/D: col = l&31, row = (r&3) + 8(r>>2) + 4(l>>5) for register r of 16. ----
 template <int DT> __device__ __forceinline__ f32x16_t mfma32(s16x8_t a, s16x8_t b, f32x16_t c) {

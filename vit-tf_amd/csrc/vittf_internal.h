@@ -26,10 +26,6 @@ int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, i
                               int32_t tokens, int32_t n_reg, int32_t part_mask, void* const outs[3], int32_t dtype,
                               hipStream_t st, int32_t* taken);
 
-// attention_fp8.hip: where the fp8 operands lie inside its workspace (filled by gemm_pp.hip's fp8 qkv epilogue)
-void vittf_fp8_ws_pointers(void* ws, int32_t batch, int32_t tokens, int32_t heads, unsigned** amax, unsigned char** q8,
-                           unsigned char** k8, unsigned char** qs, unsigned char** ks, int32_t* np);
-
 // attention_pp64.hip: attention on pre-scaled q (entry point: attention.hip)
 int vittf_attention_pp64(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
                          hipStream_t st);

@@ -18,7 +18,7 @@ from . import _lib
 
 # axis -> (sliced volume dim, (volume dim of image rows, volume dim of image cols))      infer.py:138-147
 AXIS_DIMS = {'z': (2, (0, 1)), 'y': (1, (0, 2)), 'x': (0, (1, 2))}
-# Slices per vittf_vit_k_features call.  Slices are independent and results do not depend on the batching (tested: 31 / 32 /
+# Slices per vittf_vit_features call.  Slices are independent and results do not depend on the batching (tested: 31 / 32 /
 # 256 / 512 give the same bits); larger batches amortise every launch's partial last round of workgroups.  The persistent
 # kernels of the ViT-S path hand out 128- / 256-row tiles to 256 CUs: 256 slices x 4097 tokens are 16.004 rounds of the qkv
 # projection's tiles and 32.01 of the block tail's -- a seventeenth / thirty-third round for one tile in 256 --, 512 slices
