@@ -537,6 +537,35 @@ int vittf_surface_shell(const uint8_t* labels, int32_t n0, int32_t n1, int32_t n
 int vittf_confusion_matrix(const uint8_t* target, const uint8_t* pred, int64_t n, int32_t classes, int64_t* counts,
                            void* stream);
 
+/* ---- connected components of a uint8 volume (vit-tf_amd/components.py, label_islands.py, predict_ntf.py --largest-island) --
+ * Foreground and link rule: select 0..255: the set {src == select} (as vittf_erode_mask defines it); -1: {src != 0}; -2 ("each
+ * value"): every voxel whose value is not 255 is foreground and two neighbours are linked only if they hold the same value
+ * (one call labels every cluster of a k-means volume: there 0 is a cluster and 255 the mask value of vittf_kmeans_sums).
+ * connectivity 1 = 6 face neighbours (scipy.ndimage.label's default), 2 = 18, 3 = 26: generate_binary_structure(3,
+ * connectivity), the numbering of vittf_erode_mask; anything else: VITTF_ERR_INVALID_ARG.
+ * labels int32 (n0, n1, n2), 4-byte aligned: 0 for background, else 1 + the smallest linear index (i0 * n1 + i1) * n2 + i2
+ * among the voxels of the component -- independent of any execution order: the same input gives the same bytes.
+ * n0 * n1 * n2 <= 2^31 - 2.  src may sit at any byte alignment.  ws: 4-byte aligned, >= vittf_components_workspace_bytes(n0, n1,
+ * n2) = 4 bytes per voxel rounded up to 256 (0 for a shape the call refuses); too small: VITTF_ERR_WORKSPACE.
+ * Three launches: union-find in LDS per 4 x 8 x 64 tile (n2 the fast axis), union-find over the tile seams on the global parent
+ * array (agent-scope atomics), flatten. */
+#define VITTF_CC_TILE0 4
+#define VITTF_CC_TILE1 8
+#define VITTF_CC_TILE2 64
+size_t vittf_components_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int vittf_label_components(const uint8_t* src, int32_t n0, int32_t n1, int32_t n2, int32_t select, int32_t connectivity,
+                           int32_t* labels, void* ws, size_t ws_bytes, void* stream);
+
+/* sizes[l - 1] = the number of voxels with label l, for a label volume of vittf_label_components (labels 0..nvox); sizes int32
+ * [nvox], zeroed by the call on `stream`.  Integer adds: exact and order-independent.  1 <= nvox <= 2^31 - 2; 4-byte aligned. */
+int vittf_component_sizes(const int32_t* labels, int64_t nvox, int32_t* sizes, void* stream);
+
+/* dst[v] = src[v] where labels[v] != 0 and the component is kept, else fill (0..255).  keep_label > 0: the component with that
+ * label is kept (sizes may be NULL); keep_label == 0: every component with sizes[labels[v] - 1] >= min_size.  One pass; dst may
+ * equal src.  labels, sizes: 4-byte aligned. */
+int vittf_filter_components(const uint8_t* src, const int32_t* labels, const int32_t* sizes, int64_t nvox, int32_t min_size,
+                            int32_t keep_label, int32_t fill, uint8_t* dst, void* stream);
+
 /* F.interpolate(mode='nearest') of a uint8 volume (n0, n1, n2) -> (o0, o1, o2): src index = min(floor(dst * (float)in /
  * out), in - 1) per dim.  equals < 0: plain resize -- the label up-sample of predict_ntf.py:217-218; equals = c in 0..255:
  * the resized class mask (src == c) as 0/1 -- evaluate_similarities.py:63 without materialising the full-size mask. */

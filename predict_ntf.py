@@ -44,6 +44,22 @@ def assign_labels(similarities):
     return vt.assign_labels(similarities, ct_org_thresholds)
 
 
+def pred_tag(num_samples, sampling_mode, bilateral_solver=False, largest_island=False):
+    """The tag of a run's output files: ntf_pred<tag>.npy, ntf_metrics<tag>.json."""
+    return f"{num_samples}{sampling_mode}{'bls' if bilateral_solver else ''}{'isl' if largest_island else ''}"
+
+
+def keep_largest_islands(similarities, connectivity=1):
+    """Every class map kept inside the largest island of the set the label rule thresholds (map > int(t * 255), the
+    threshold vt.assign_labels applies to that class) and 0 elsewhere; classes beyond the thresholds are left as they are."""
+    out = {}
+    for i, (k, v) in enumerate(similarities.items()):
+        if i < len(ct_org_thresholds):
+            v = vt.components.largest_island(torch.as_tensor(v), int(ct_org_thresholds[i] * 255), connectivity)
+        out[k] = v
+    return out
+
+
 def _metrics(labels, pred, names):
     """(:228-246) accuracy, per-class precision / recall / F1 / IoU and the confusion matrix (counted on the GPU)."""
     acc, prec, rec, f1, iou, cm = vt.scores.scores(labels, pred)
@@ -74,6 +90,7 @@ def main(argv=None):
     parser = ArgumentParser()
     parser.add_argument('--data', type=str, help='directory holding volume, features and annotations / labels')
     parser.add_argument('--bilateral-solver', action='store_true', help='refine every class map with the 3-D bilateral solver')
+    parser.add_argument('--largest-island', action='store_true', help='keep every class map only inside the largest island of its thresholded set')
     parser.add_argument('--load-sims', action='store_true', help='reuse a similarities file written by an earlier run')
     parser.add_argument('--num-samples', type=float, default=0.0, help='annotations sampled per class from the labels (0: use the annotation file)')
     parser.add_argument('--sampling-mode', type=str, choices=['uniform', 'surface', 'both'], default='both', help='where samples are drawn from')
@@ -82,8 +99,7 @@ def main(argv=None):
     d = Path(args.data)
     if args.num_samples == 0.0:
         args.sampling_mode = 'annotated'
-    bls = 'bls' if args.bilateral_solver else ''
-    tag = f'{args.num_samples}{args.sampling_mode}{bls}'
+    tag = pred_tag(args.num_samples, args.sampling_mode, args.bilateral_solver, args.largest_island)
     if (d / f'ntf_pred{tag}.npy').exists():
         print(f'Already inferred NTF preds for {d} using sampling mode {args.sampling_mode} and {args.num_samples} samples')
         sys.exit(0)
@@ -125,6 +141,10 @@ def main(argv=None):
     if args.load_sims:
         similarities = {k: torch.as_tensor(v) for k, v in np.load(d / 'similarities.npy', allow_pickle=True)[()].items()}
         t2 = t1
+        if args.largest_island:
+            similarities = keep_largest_islands(similarities)
+            torch.cuda.synchronize()
+            t2 = time.time()
     else:
         t1 = time.time()
         if sum(int(torch.as_tensor(v).shape[0]) for v in annotations.values()) > 10000:     # (:185-187) one class per call
@@ -133,6 +153,8 @@ def main(argv=None):
         else:
             similarities = compute_similarities(volume, features, annotations, bilateral_solver=args.bilateral_solver,
                                                 keep_on_device=True)
+        if args.largest_island:
+            similarities = keep_largest_islands(similarities)
         torch.cuda.synchronize()
         t2 = time.time()
     print('Similarities:', {k: v.shape for k, v in similarities.items()})

@@ -124,6 +124,10 @@ SIGNATURES = {
     'vittf_surface_shell_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'vittf_surface_shell': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     'vittf_confusion_matrix': (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    'vittf_components_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'vittf_label_components': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'vittf_component_sizes': (C.c_int, [_vp, _i64, _vp, _vp]),
+    'vittf_filter_components': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     'vittf_resize_nearest_u8': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     'vittf_widen_f16': (C.c_int, [_vp, _i64, _vp, _vp]),
     'vittf_bilateral_workspace_bytes': (_sz, [_i32, _i32, _i32, C.c_double, _i32]),
@@ -164,6 +168,7 @@ QUERY_MAX_A = 64          # VITTF_QUERY_MAX_A: annotations of a vittf_similarity
 GRAM_RUN = 2048           # VITTF_GRAM_RUN: voxels per fp32 accumulation run of vittf_feature_gram
 PCA_MAX_K = 64            # VITTF_PCA_MAX_K: components of one vittf_feature_project call
 KMEANS_MAX_C = 64         # VITTF_KMEANS_MAX_C: clusters of one vittf_kmeans_assign / vittf_kmeans_sums call
+CC_TILE = (4, 8, 64)      # VITTF_CC_TILE0..2: the tile of vittf_label_components' LDS pass, voxels along (n0, n1, n2)
 KMEANS_SPANS = 128        # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
