@@ -517,6 +517,40 @@ size_t vittf_kmeans_sums_workspace_bytes(int32_t f, int64_t nvox, int32_t c);
 int vittf_kmeans_sums(const uint16_t* feat, int32_t f, int64_t nvox, const uint8_t* labels, int32_t c, double* sums,
                       int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Support-vector classification of a feature volume (vit-tf_amd/svm.py, classify_features.py): the decision pass of a
+ * one-vs-one C-SVC as libsvm and scikit-learn define it.  classes = C in 2..VITTF_SVM_MAX_CLASSES; the P = C (C - 1) / 2
+ * pairs are ordered (0,1), (0,2), ..., (C-2,C-1); for pair p = (i, j) a decision dec_p > 0 votes for i, anything else
+ * (exactly 0 included) for j; the label is the class with the most votes, the lowest index among equal counts.
+ * feat, nvox: as for the PCA entries above (fp16 [f][nvox], 2-byte aligned, nvox >= 1; rows that are not 16-byte aligned take
+ * a slower load path).  voxel_norm: NULL or the vittf_voxel_norm array: the voxel is then x / norm, as in vittf_similarity.
+ * labels uint8 [nvox] (0..C-1, any alignment); decision NULL or fp32 [P][nvox].  The labels are the vote over exactly the
+ * fp32 values the call writes to `decision`, and the same bytes whether it is NULL or not; fixed summation order and no
+ * floating-point atomics: the same call gives the same bytes.  The volume is read once.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_SVM_MAX_CLASSES 8   /* most classes of one model: 28 pairs, the decisions of a voxel fill one 32-row MFMA tile */
+#define VITTF_SVM_MAX_SV 65536    /* most support vectors of one model */
+
+/* RBF kernel: dec_p(x) = sum_s pair_coef[p][s] exp(-gamma |x - sv_s|^2) + intercept[p].  sv fp16 [n_sv][f] (the fit rounds
+ * its samples to fp16 first, so these are the model's vectors exactly), pair_coef fp32 [P][n_sv], dense, zero where the
+ * support vector's class is not in the pair; intercept fp32 [P]; 1 <= n_sv <= VITTF_SVM_MAX_SV; gamma >= 0, finite.
+ * f a multiple of 32 in 32..768 (padded inside with zero features to 32, 128, 384 or 768; reduce a wider volume first).
+ * sv . x: fp16 MFMAs with fp32 accumulation; the exponential is one v_exp_f32; the second contraction runs on the matrix
+ * cores with the kernel values and the (power-of-two scaled) coefficients as fp16 hi + lo halves (2^-22 relative).
+ * Three launches (coefficient scale, support-vector images, decision).  ws: 16-byte aligned, >=
+ * vittf_svm_rbf_workspace_bytes(f, n_sv, classes) = 256 + ceil(n_sv / 32) x (64 FP + 5760) bytes (0 for a shape the call
+ * refuses); too small: VITTF_ERR_WORKSPACE. */
+size_t vittf_svm_rbf_workspace_bytes(int32_t f, int32_t n_sv, int32_t classes);
+int vittf_svm_rbf_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint16_t* sv, const float* pair_coef,
+                         const float* intercept, int32_t n_sv, int32_t classes, float gamma, const float* voxel_norm,
+                         uint8_t* labels, float* decision, void* ws, size_t ws_bytes, void* stream);
+
+/* Linear kernel: dec_p(x) = w[p] . x + intercept[p], w fp32 [P][f] = sum_s pair_coef[p][s] sv_s folded on the host, taken as
+ * fp16 hi + lo halves (to 2^-22 relative) with fp32 accumulation: vittf_kmeans_assign's score loop with the vote behind it
+ * instead of the arg-max.  f a multiple of 32 in 32..1024. */
+int vittf_svm_linear_decide(const uint16_t* feat, int32_t f, int64_t nvox, const float* w, const float* intercept,
+                            int32_t classes, const float* voxel_norm, uint8_t* labels, float* decision, void* stream);
+
 /* ---- label-volume helpers: sampler candidate masks and scores --------------------------- */
 /* dst = binary_erosion(set, generate_binary_structure(3, connectivity)) with scipy.ndimage's defaults (one iteration,
  * border_value 0): set = {src == class_id} (class_id 0..255) or {src != 0} (class_id < 0); uint8 volumes (n0, n1, n2),

@@ -118,6 +118,9 @@ SIGNATURES = {
     'vittf_kmeans_assign': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     'vittf_kmeans_sums_workspace_bytes': (_sz, [_i32, _i64, _i32]),
     'vittf_kmeans_sums': (C.c_int, [_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_svm_rbf_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'vittf_svm_rbf_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_svm_linear_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     'vittf_topk_voxels': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
     'vittf_mean_pairwise_distance': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     'vittf_erode_mask': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -169,6 +172,8 @@ GRAM_RUN = 2048           # VITTF_GRAM_RUN: voxels per fp32 accumulation run of 
 PCA_MAX_K = 64            # VITTF_PCA_MAX_K: components of one vittf_feature_project call
 KMEANS_MAX_C = 64         # VITTF_KMEANS_MAX_C: clusters of one vittf_kmeans_assign / vittf_kmeans_sums call
 CC_TILE = (4, 8, 64)      # VITTF_CC_TILE0..2: the tile of vittf_label_components' LDS pass, voxels along (n0, n1, n2)
+SVM_MAX_CLASSES = 8       # VITTF_SVM_MAX_CLASSES: classes of one vittf_svm_*_decide model (28 one-vs-one pairs)
+SVM_MAX_SV = 65536        # VITTF_SVM_MAX_SV: support vectors of one vittf_svm_rbf_decide model
 KMEANS_SPANS = 128        # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
