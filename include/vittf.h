@@ -350,7 +350,8 @@ int64_t vittf_attention_rescale_count(int32_t reset);
  * q_prescaled = 1, computed with OCP e4m3 operands on v_mfma_scale_f32_32x32x64_f8f6f4: per (slice, head) power-of-two
  * scales for q, k and v (absmax / 448, applied by the instruction's scale operands), fp32 softmax statistics and
  * accumulators, P as fp8.  Error of the attention output ~3e-2 relative (3-bit mantissas):
- * an opt-in, never the default.  ws: vittf_attention_fp8_workspace_bytes(batch, tokens, heads) bytes, 256-byte aligned. */
+ * an opt-in, never the default.  That figure is for a diffuse softmax; it grows with the magnitude of the logits (a 2^-4
+ * relative operand error on a score of several hundred exp2 units moves the weights of a peaked row).  ws: vittf_attention_fp8_workspace_bytes(batch, tokens, heads) bytes, 256-byte aligned. */
 size_t vittf_attention_fp8_workspace_bytes(int32_t batch, int32_t tokens, int32_t heads);
 int vittf_attention_fp8(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype, void* ws,
                         size_t ws_bytes, void* stream);
