@@ -1,8 +1,10 @@
-"""Support-vector classification of a feature volume from annotated voxels: a learned label volume.
+"""Support-vector or random-forest classification of a feature volume from annotated voxels: a learned label volume.
 
-    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--kernel {rbf,linear}] [--C 1.0]
-                                [--gamma scale|FLOAT] [--normalize] [--background {auto,labels,border,none}] [--tol T] [--model FILE]
-                                [--seed S] [--overwrite]
+    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest}]
+                                [--kernel {rbf,linear}] [--C 1.0] [--gamma scale|FLOAT] [--normalize] [--tol T]
+                                [--trees 256] [--max-depth N] [--max-features sqrt|all|INT|FRACTION] [--min-samples-leaf 1]
+                                [--no-bootstrap] [--votes]
+                                [--background {auto,labels,border,none}] [--model FILE] [--seed S] [--overwrite]
 
 DIR follows predict_ntf.py's directory contract: ``volume.npy`` and ``labels.npy`` (flipped on axis -3), the largest file
 whose name contains ``features`` and not ``pred``, and ``annotations.npy`` when ``--num-samples 0`` (otherwise the annotations
@@ -21,6 +23,17 @@ Outputs in DIR, with the tag ``<num><mode>_<kernel>[_norm][_nobg]``:
   * ``svm_metrics<tag>.json`` when labels.npy exists: the keys of ntf_metrics*.json plus fit_time, predict_time and n_sv, the
     prediction nearest-resized to the label volume.
 The same directory and flags give the same bytes.  There is no CPU path.
+
+``--classifier forest`` trains a random forest instead (vt.forest.fit: CART on the host, slower than scikit-learn's; the pass
+over the volume is libvittf's vittf_forest_decide, forest.hip) on the same samples, background class and seed.  It has no
+gamma or C, no F <= 768 limit and does not care how the features are scaled.  ``--kernel``, ``--C``, ``--gamma`` and ``--tol``
+do not apply (given explicitly they are refused), ``--normalize`` is not built for it.  ``--model FILE`` picks the classifier
+by the file.  Outputs, with the tag ``<num><mode>_rf<trees>[_d<depth>][_all|_mf<k>][_nobg]`` (``_all``: --max-features all;
+``_mf<k>``: any other value than sqrt):
+  * ``rf_pred<tag>.npy``, ``rf_model<tag>.npz`` (vt.forest.save_model), ``rf_metrics<tag>.json`` (n_trees, n_nodes and max_depth
+    in the place of n_sv): as the SVM's;
+  * with ``--votes``, ``rf_votes<tag>.npy``: uint8 (C, W', H', D'), votes * 255 // (trees * 65535) per class in the order of the
+    model's classes (ascending label value) -- a confidence volume for thresholds or the bilateral solver.
 """
 import json
 import sys
@@ -48,6 +61,17 @@ def output_paths(d, tag):
     return d / f'svm_pred{tag}.npy', d / f'svm_model{tag}.npz', d / f'svm_metrics{tag}.json'
 
 
+def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='sqrt', background=True):
+    """The tag of a forest run's output files: rf_pred<tag>.npy, rf_model<tag>.npz, rf_metrics<tag>.json, rf_votes<tag>.npy."""
+    mf = '' if max_features == 'sqrt' else '_all' if max_features == 'all' else f'_mf{max_features}'
+    return f"{num_samples}{sampling_mode}_rf{trees}{'' if max_depth is None else f'_d{max_depth}'}{mf}{'' if background else '_nobg'}"
+
+
+def forest_paths(d, tag):
+    d = Path(d)
+    return d / f'rf_pred{tag}.npy', d / f'rf_model{tag}.npz', d / f'rf_metrics{tag}.json', d / f'rf_votes{tag}.npy'
+
+
 def find_feature_file(d):
     """predict_ntf.py's rule: the largest file whose name contains 'features' and not 'pred'; None when there is none."""
     fns = [p for p in Path(d).iterdir() if 'features' in p.name and 'pred' not in p.name]
@@ -65,17 +89,147 @@ def _draw(mode, lab, n, class_id=None):
     return sampling_modes[mode](lab, n, thin_to_reasonable=True, class_id=class_id)
 
 
+SVM_DEFAULTS = {'kernel': 'rbf', 'C': 1.0, 'gamma': 'scale', 'tol': 1e-3}
+
+
+class _Svm:
+    """The support-vector side of main: its argument checks, file names, fit, pass over the volume and report."""
+    name, module = 'SVM', vt.svm
+
+    def __init__(self, args):
+        for k, v in SVM_DEFAULTS.items():
+            if getattr(args, k) is None:
+                setattr(args, k, v)
+        self.args, self.model = args, None
+        if not (args.C > 0 and np.isfinite(args.C)):
+            _fail('C', f'{args.C} is not a positive number')
+        if not (args.tol > 0 and np.isfinite(args.tol)):
+            _fail('tol', f'{args.tol} is not a positive number')
+        self.gamma = args.gamma
+        if self.gamma != 'scale':
+            try:
+                self.gamma = float(self.gamma)
+            except ValueError:
+                _fail('gamma', f"{args.gamma!r} is neither 'scale' nor a number")
+            if not (np.isfinite(self.gamma) and self.gamma >= 0):
+                _fail('gamma', f'{args.gamma} is negative or not finite')
+
+    def configure(self, with_bg):
+        """Called once the background decision is known (a loaded model brings its own): fixes the tag's ingredients."""
+        m = self.model
+        self.kernel, self.normalize = (self.args.kernel, self.args.normalize) if m is None else (m.kernel, m.normalize)
+        self.with_bg = with_bg
+
+    def paths(self, d, num_samples, mode):
+        return output_paths(d, svm_tag(num_samples, mode, self.kernel, self.normalize, self.with_bg))
+
+    def check_features(self, f, name):
+        if self.kernel == 'rbf' and f > 768:
+            _fail('kernel', f'the RBF kernel takes F <= 768, {name} has F = {f}: reduce it first (reduce_features.py)')
+        if self.model is not None and self.model.sv.shape[1] != f:
+            _fail('model', f'fitted on F = {self.model.sv.shape[1]} features, {name} has F = {f}')
+
+    def fit(self, samples, targets, names):
+        a = self.args
+        return vt.svm.fit(samples, targets, kernel=self.kernel, C=a.C, gamma=self.gamma, tol=a.tol, normalize=self.normalize,
+                          class_names=names)
+
+    def predict(self, features, model, paths):
+        return vt.svm.predict(features, model)
+
+    def describe(self, model):
+        return f'{model.sv.shape[0]} support vectors ({model.n_support.tolist()} per class)'
+
+    def metrics(self, model):
+        return {'n_sv': int(model.sv.shape[0])}
+
+
+class _Forest:
+    """The random-forest side of main."""
+    name, module = 'RF', vt.forest
+
+    def __init__(self, args):
+        self.args, self.model = args, None
+        for k in SVM_DEFAULTS:
+            if getattr(args, k) is not None:
+                _fail(k, 'does not apply to --classifier forest')
+        if args.normalize:
+            _fail('normalize', 'is not built for --classifier forest')
+        if not 1 <= args.trees <= vt._lib.FOREST_MAX_TREES:
+            _fail('trees', f'{args.trees} is outside 1..{vt._lib.FOREST_MAX_TREES}')
+        if args.max_depth is not None and not 1 <= args.max_depth <= vt._lib.FOREST_MAX_DEPTH:
+            _fail('max-depth', f'{args.max_depth} is outside 1..{vt._lib.FOREST_MAX_DEPTH}')
+        if args.min_samples_leaf < 1:
+            _fail('min-samples-leaf', f'{args.min_samples_leaf} is not positive')
+        mf = args.max_features
+        if mf not in ('sqrt', 'all'):
+            try:
+                mf = int(mf)
+            except ValueError:
+                try:
+                    mf = float(mf)
+                except ValueError:
+                    _fail('max-features', f"{args.max_features!r} is none of 'sqrt', 'all', an integer, a fraction")
+            if not (mf >= 1 if isinstance(mf, int) else 0.0 < mf <= 1.0):
+                _fail('max-features', f'{args.max_features} is neither an integer of at least 1 nor a fraction in (0, 1]')
+        self.max_features = mf
+        print('Note: --kernel, --C, --gamma and --tol do not apply to --classifier forest')
+
+    def configure(self, with_bg):
+        self.with_bg = with_bg
+
+    def paths(self, d, num_samples, mode):
+        a, m = self.args, self.model
+        if m is not None:                                     # a loaded forest: what the file can tell
+            tag = forest_tag(num_samples, mode, m.trees, None, 'sqrt', self.with_bg)
+        else:
+            tag = forest_tag(num_samples, mode, a.trees, a.max_depth, self.max_features, self.with_bg)
+        return forest_paths(d, tag)
+
+    def check_features(self, f, name):
+        if self.model is not None and self.model.n_features != f:
+            _fail('model', f'fitted on F = {self.model.n_features} features, {name} has F = {f}')
+        if self.model is None and isinstance(self.max_features, int) and self.max_features > f:
+            _fail('max-features', f'{self.max_features} is more than the F = {f} of {name}')
+
+    def fit(self, samples, targets, names):
+        a = self.args
+        return vt.forest.fit(samples, targets, trees=a.trees, max_features=self.max_features, max_depth=a.max_depth,
+                             min_samples_leaf=a.min_samples_leaf, bootstrap=not a.no_bootstrap, seed=a.seed, class_names=names)
+
+    def predict(self, features, model, paths):
+        if not self.args.votes:
+            return vt.forest.predict(features, model)
+        idx, votes = vt.forest.predict(features, model, return_votes=True)
+        wide = votes.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        np.save(paths[3], (wide * 255 // (model.trees * 65535)).to(torch.uint8).cpu().numpy())
+        return idx
+
+    def describe(self, model):
+        return f'{model.trees} trees, {model.n_nodes} nodes, depth {model.max_depth}'
+
+    def metrics(self, model):
+        return {'n_trees': model.trees, 'n_nodes': model.n_nodes, 'max_depth': model.max_depth}
+
+
 def main(argv=None):
-    parser = ArgumentParser('Classify a feature volume with a support-vector machine trained on annotated voxels')
+    parser = ArgumentParser('Classify a feature volume with a support-vector machine or a random forest trained on annotated voxels')
     parser.add_argument('--data', type=str, required=True, help='directory holding volume, features and annotations / labels')
     parser.add_argument('--num-samples', type=float, default=0.0, help='annotations sampled per class from the labels (0: use the annotation file)')
     parser.add_argument('--sampling-mode', type=str, choices=['uniform', 'surface', 'both'], default='both', help='where samples are drawn from')
-    parser.add_argument('--kernel', type=str, choices=list(vt.svm.KERNELS), default='rbf')
-    parser.add_argument('--C', type=float, default=1.0, help='box constraint of the C-SVC')
-    parser.add_argument('--gamma', type=str, default='scale', help="RBF width: 'scale' (1 / (F var(samples))) or a number")
+    parser.add_argument('--classifier', type=str, choices=['svm', 'forest'], default=None, help='svm (the default) or forest; --model FILE implies it')
+    parser.add_argument('--kernel', type=str, choices=list(vt.svm.KERNELS), default=None, help='svm: rbf (default) or linear')
+    parser.add_argument('--C', type=float, default=None, help='svm: box constraint of the C-SVC (default 1.0)')
+    parser.add_argument('--gamma', type=str, default=None, help="svm: RBF width: 'scale' (1 / (F var(samples)), default) or a number")
     parser.add_argument('--normalize', action='store_true', help='L2-normalise every voxel first (cosine geometry)')
     parser.add_argument('--background', type=str, choices=['auto', 'labels', 'border', 'none'], default='auto', help='where the background class is drawn from')
-    parser.add_argument('--tol', type=float, default=1e-3, metavar='T', help='largest KKT violation the solver stops at')
+    parser.add_argument('--tol', type=float, default=None, metavar='T', help='svm: largest KKT violation the solver stops at (default 1e-3)')
+    parser.add_argument('--trees', type=int, default=256, help='forest: number of trees')
+    parser.add_argument('--max-depth', type=int, default=None, metavar='N', help='forest: deepest level of a tree (default: fully grown)')
+    parser.add_argument('--max-features', type=str, default='sqrt', help="forest: features tried per node: 'sqrt', 'all', an integer or a fraction")
+    parser.add_argument('--min-samples-leaf', type=int, default=1, help='forest: fewest training rows of a leaf')
+    parser.add_argument('--no-bootstrap', action='store_true', help='forest: every tree sees every sample once')
+    parser.add_argument('--votes', action='store_true', help='forest: also write the per-class vote shares rf_votes<tag>.npy')
     parser.add_argument('--model', type=str, default=None, metavar='FILE', help='apply this saved model instead of fitting')
     parser.add_argument('--seed', type=int, default=0, help='seed of the sample draws')
     parser.add_argument('--overwrite', action='store_true', help='replace existing output files')
@@ -86,22 +240,17 @@ def main(argv=None):
         _fail('data', f'{d} is not a directory')
     if not args.num_samples >= 0:
         _fail('num-samples', f'{args.num_samples} is negative')
-    if not (args.C > 0 and np.isfinite(args.C)):
-        _fail('C', f'{args.C} is not a positive number')
-    if not (args.tol > 0 and np.isfinite(args.tol)):
-        _fail('tol', f'{args.tol} is not a positive number')
-    gamma = args.gamma
-    if gamma != 'scale':
-        try:
-            gamma = float(gamma)
-        except ValueError:
-            _fail('gamma', f"{args.gamma!r} is neither 'scale' nor a number")
-        if not (np.isfinite(gamma) and gamma >= 0):
-            _fail('gamma', f'{args.gamma} is negative or not finite')
     model = None
+    kind = args.classifier
+    if args.model:
+        of_file = 'forest' if vt.forest.is_forest_file(args.model) else 'svm'
+        if kind is not None and kind != of_file:
+            _fail('model', f'{args.model} does not hold a {kind} model')
+        kind = of_file
+    clf = (_Forest if kind == 'forest' else _Svm)(args)       # the classifier's own argument checks come first
     if args.model:
         try:
-            model = vt.svm.load_model(args.model)
+            model = clf.model = clf.module.load_model(args.model)
         except (OSError, ValueError, KeyError) as e:
             _fail('model', e)
     has_labels = (d / 'labels.npy').exists()
@@ -115,14 +264,15 @@ def main(argv=None):
             _fail('num-samples', f'Cannot sample labels if they are not provided ({d} has no labels.npy)')
         if args.num_samples == 0 and not (d / 'annotations.npy').exists():
             _fail('num-samples', f'0 asks for the annotation file, {d} has no annotations.npy')
-        kernel, normalize, with_bg = args.kernel, args.normalize, background != 'none'
+        with_bg = background != 'none'
     else:
-        kernel, normalize, with_bg = model.kernel, model.normalize, bool(model.labels[0] == 0)
+        with_bg = bool(model.labels[0] == 0)
+    clf.configure(with_bg)
     mode = 'annotated' if args.num_samples == 0.0 else args.sampling_mode
-    tag = svm_tag(args.num_samples, mode, kernel, normalize, with_bg)
-    pred_path, model_path, metrics_path = output_paths(d, tag)
+    paths = clf.paths(d, args.num_samples, mode)
+    pred_path, model_path, metrics_path = paths[:3]
     if pred_path.exists() and not args.overwrite:
-        print(f'Already inferred SVM preds for {d} using sampling mode {mode} and {args.num_samples} samples')
+        print(f'Already inferred {clf.name} preds for {d} using sampling mode {mode} and {args.num_samples} samples')
         sys.exit(0)
     if not (d / 'volume.npy').exists():
         _fail('data', f'{d} has no volume.npy')
@@ -138,10 +288,7 @@ def main(argv=None):
     f = int(features.shape[0])
     if features.ndim != 4 or f % 32 or not 32 <= f <= 1024:
         _fail('data', f'{feat_fn.name} holds {tuple(features.shape)}: F = {f} is not a multiple of 32 in 32..1024')
-    if kernel == 'rbf' and f > 768:
-        _fail('kernel', f'the RBF kernel takes F <= 768, {feat_fn.name} has F = {f}: reduce it first (reduce_features.py)')
-    if model is not None and model.sv.shape[1] != f:
-        _fail('model', f'fitted on F = {model.sv.shape[1]} features, {feat_fn.name} has F = {f}')
+    clf.check_features(f, feat_fn.name)
 
     torch.manual_seed(args.seed)
     t0 = time.time()
@@ -174,26 +321,25 @@ def main(argv=None):
                 values.append(0)
         if len(values) < 2 or len(values) > vt._lib.SVM_MAX_CLASSES:
             _fail('data', f'{len(values)} classes (background included): the classifier takes 2..{vt._lib.SVM_MAX_CLASSES}')
-        samples, targets = vt.svm.sample(features, annotations, vol_shape, normalize)
+        samples, targets = vt.svm.sample(features, annotations, vol_shape, args.normalize)
         order = np.argsort(values)                                         # class names in ascending label value
         try:
-            model = vt.svm.fit(samples, np.asarray(values)[targets], kernel=kernel, C=args.C, gamma=gamma, tol=args.tol,
-                               normalize=normalize, class_names=[list(annotations)[i] for i in order])
+            model = clf.fit(samples, np.asarray(values)[targets], [list(annotations)[i] for i in order])
         except ValueError as e:
             _fail('num-samples', e)
     t1 = time.time()
-    pred_idx = vt.svm.predict(features, model)
+    pred_idx = clf.predict(features, model, paths)
     pred = torch.from_numpy(model.labels).to(pred_idx.device)[pred_idx.long()].contiguous()
     torch.cuda.synchronize()
     t2 = time.time()
     pred = pred.cpu().numpy()
     np.save(pred_path, pred)
     if not args.model:
-        vt.svm.save_model(model, model_path)
-    print(f'Pred: {pred.shape} uint8, classes {model.class_names} as {model.labels.tolist()}, {model.sv.shape[0]} support vectors '
-          f'({model.n_support.tolist()} per class); saving to: {pred_path}')
-    print('SVM fit time:', t1 - t0)
-    print('SVM predict time:', t2 - t1)
+        clf.module.save_model(model, model_path)
+    print(f'Pred: {pred.shape} uint8, classes {model.class_names} as {model.labels.tolist()}, {clf.describe(model)}; '
+          f'saving to: {pred_path}')
+    print(f'{clf.name} fit time:', t1 - t0)
+    print(f'{clf.name} predict time:', t2 - t1)
     if labels is None:
         sys.exit(0)
     if tuple(pred.shape) != tuple(labels.shape[-3:]):
@@ -203,8 +349,8 @@ def main(argv=None):
     metrics = _metrics(labels, pred, [by_value.get(v, 'background' if v == 0 else f'ntf{v}') for v in range(n_names)])
     metrics['fit_time'] = t1 - t0
     metrics['predict_time'] = t2 - t1
-    metrics['n_sv'] = int(model.sv.shape[0])
-    print('SVM Metrics:')
+    metrics.update(clf.metrics(model))
+    print(f'{clf.name} Metrics:')
     pprint(metrics)
     with open(metrics_path, 'w') as fh:
         json.dump(metrics, fh)

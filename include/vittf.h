@@ -552,6 +552,37 @@ int vittf_svm_rbf_decide(const uint16_t* feat, int32_t f, int64_t nvox, const ui
 int vittf_svm_linear_decide(const uint16_t* feat, int32_t f, int64_t nvox, const float* w, const float* intercept,
                             int32_t classes, const float* voxel_norm, uint8_t* labels, float* decision, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Random-forest classification of a feature volume (vit-tf_amd/forest.py, classify_features.py --classifier forest): the
+ * pass of a fitted forest of binary decision trees over every voxel, scikit-learn's soft vote in integers.
+ * feat, nvox: as above (fp16 [f][nvox], finite, 2-byte aligned, nvox >= 1, f a multiple of 32 in 32..1024; rows that are
+ * not 16-byte aligned take scalar loads).  The packed forest (forest.py's pack() writes it from a validated model):
+ *   tree_offset  uint32 [trees + 1]: tree t owns nodes[tree_offset[t] .. tree_offset[t + 1]), node 0 of it is its root;
+ *                at most VITTF_FOREST_MAX_NODES nodes a tree
+ *   nodes        two uint32 per node (8 bytes, 8-byte aligned).
+ *                inner node: word 0 = feature | threshold << 16 (feature < f; threshold: the bits of an fp16, not NaN),
+ *                            word 1 = left | right << 16, indices inside the tree, BOTH LARGER than the node's own;
+ *                leaf:       word 0 = 0xFFFF, word 1 = the row of the leaf in leaf_values
+ *   leaf_values  uint16 [leaves][8] (16-byte aligned): floor(p_c 65535 + 0.5) of the leaf's class shares p_c, zeros behind
+ *                the last class
+ * A voxel goes LEFT at an inner node when feat[feature][voxel] <= threshold, the two compared as fp16 numbers (-0 == +0;
+ * a threshold of +inf sends everything left, -inf everything right).  For fp16 x and any real t, x <= t exactly when
+ * x <= the largest fp16 <= t: a forest fitted in fp32 or fp64 converts without changing a decision.  votes[c][v] is the
+ * uint32 sum over the trees of leaf_values[leaf][c] (trees <= 4096: at most 4096 x 65535 < 2^32); labels[v] the class with
+ * the largest vote, the lowest index among equal votes.  max_depth, 0..VITTF_FOREST_MAX_DEPTH, is the depth of the deepest
+ * tree (a single leaf has depth 0): a walk takes at most max_depth steps whatever the nodes say, and one that has not
+ * reached a leaf by then casts no vote for its tree.  votes may be NULL; the labels are the same.  Integer arithmetic
+ * only, no atomics: the same call gives the same bytes.  One launch, no workspace; the volume is read once.
+ * Workgroups of 1024 threads own 1024, 512, 256, 128 or 64 voxels (f <= 64, 128, 256, 512, 1024), staged in a 128 KiB LDS tile.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_FOREST_MAX_CLASSES 8       /* most classes of one forest: a leaf row is one 16-byte load */
+#define VITTF_FOREST_MAX_TREES 4096      /* most trees: the uint32 votes cannot overflow */
+#define VITTF_FOREST_MAX_NODES 65535     /* most nodes of one tree: child indices are 16 bits */
+#define VITTF_FOREST_MAX_DEPTH 64        /* largest max_depth */
+int vittf_forest_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint32_t* nodes, const uint16_t* leaf_values,
+                        const uint32_t* tree_offset, int32_t trees, int32_t classes, int32_t max_depth, uint8_t* labels,
+                        uint32_t* votes, void* stream);
+
 /* ---- label-volume helpers: sampler candidate masks and scores --------------------------- */
 /* dst = binary_erosion(set, generate_binary_structure(3, connectivity)) with scipy.ndimage's defaults (one iteration,
  * border_value 0): set = {src == class_id} (class_id 0..255) or {src != 0} (class_id < 0); uint8 volumes (n0, n1, n2),

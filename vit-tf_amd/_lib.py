@@ -121,6 +121,7 @@ SIGNATURES = {
     'vittf_svm_rbf_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'vittf_svm_rbf_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_svm_linear_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    'vittf_forest_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     'vittf_topk_voxels': (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
     'vittf_mean_pairwise_distance': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     'vittf_erode_mask': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -174,6 +175,10 @@ KMEANS_MAX_C = 64         # VITTF_KMEANS_MAX_C: clusters of one vittf_kmeans_ass
 CC_TILE = (4, 8, 64)      # VITTF_CC_TILE0..2: the tile of vittf_label_components' LDS pass, voxels along (n0, n1, n2)
 SVM_MAX_CLASSES = 8       # VITTF_SVM_MAX_CLASSES: classes of one vittf_svm_*_decide model (28 one-vs-one pairs)
 SVM_MAX_SV = 65536        # VITTF_SVM_MAX_SV: support vectors of one vittf_svm_rbf_decide model
+FOREST_MAX_CLASSES = 8    # VITTF_FOREST_MAX_CLASSES: classes of one vittf_forest_decide model (a leaf row is 8 x uint16)
+FOREST_MAX_TREES = 4096   # VITTF_FOREST_MAX_TREES: trees of one model (4096 x 65535 < 2^32: the uint32 votes cannot overflow)
+FOREST_MAX_NODES = 65535  # VITTF_FOREST_MAX_NODES: nodes of one tree (16-bit child indices)
+FOREST_MAX_DEPTH = 64     # VITTF_FOREST_MAX_DEPTH: the deepest tree vittf_forest_decide walks
 KMEANS_SPANS = 128        # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
