@@ -3,7 +3,7 @@
     python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest}]
                                 [--kernel {rbf,linear}] [--C 1.0] [--gamma scale|FLOAT] [--normalize] [--tol T]
                                 [--trees 256] [--max-depth N] [--max-features sqrt|all|INT|FRACTION] [--min-samples-leaf 1]
-                                [--no-bootstrap] [--votes]
+                                [--no-bootstrap] [--votes] [--features {dino,handcrafted,intensity}]
                                 [--background {auto,labels,border,none}] [--model FILE] [--seed S] [--overwrite]
 
 DIR follows predict_ntf.py's directory contract: ``volume.npy`` and ``labels.npy`` (flipped on axis -3), the largest file
@@ -34,6 +34,19 @@ by the file.  Outputs, with the tag ``<num><mode>_rf<trees>[_d<depth>][_all|_mf<
     in the place of n_sv): as the SVM's;
   * with ``--votes``, ``rf_votes<tag>.npy``: uint8 (C, W', H', D'), votes * 255 // (trees * 65535) per class in the order of the
     model's classes (ascending label value) -- a confidence volume for thresholds or the bilateral solver.
+
+``--features handcrafted`` classifies the VOLUME ITSELF instead of a feature file: the reference baseline's default mode
+(predict_svm_rf.py:25-65), an 11-channel vector per voxel at the volume's full resolution -- intensity, gradient magnitude, the
+six neighbours and the position, each standardised over the volume (vt.voxel_features; libvittf's voxel_features.hip).
+``--features intensity`` is the standardised intensity alone (the reference feeds the raw intensity there: a deliberate
+difference -- standardising is an increasing affine map, which leaves a forest's decisions and an RBF machine with
+gamma = scale unchanged up to rounding, and it keeps CT-range values representable in fp16).  No feature file is looked for;
+the training rows are the features of the annotated voxels themselves, the pass streams the volume slab by slab through the
+same decision kernels, and the prediction has the volume's own grid.  ``--normalize`` is refused.  The tag gets ``_hand`` or
+``_intensity`` directly behind ``<num><mode>`` (``svm_pred200.0both_hand_rbf.npy``, ``rf_pred200.0both_intensity_rf256.npy``).
+``--model FILE`` standardises the new volume with that volume's own statistics, as the reference does for every volume; the
+model must have F = 32 (the rows are embedded in a zeroed 32-row matrix).  A model file does not say which features it was
+fitted on: a ``_pca32`` model and a hand-crafted one both have F = 32, keeping them apart is the caller's business.
 """
 import json
 import sys
@@ -49,11 +62,12 @@ import vit_tf_amd as vt
 from predict_ntf import pick_features, sampling_modes, _metrics
 
 BORDER = 4
+FEATURE_TAGS = {'dino': '', 'handcrafted': '_hand', 'intensity': '_intensity'}
 
 
-def svm_tag(num_samples, sampling_mode, kernel, normalize=False, background=True):
+def svm_tag(num_samples, sampling_mode, kernel, normalize=False, background=True, features='dino'):
     """The tag of a run's output files: svm_pred<tag>.npy, svm_model<tag>.npz, svm_metrics<tag>.json."""
-    return f"{num_samples}{sampling_mode}_{kernel}{'_norm' if normalize else ''}{'' if background else '_nobg'}"
+    return f"{num_samples}{sampling_mode}{FEATURE_TAGS[features]}_{kernel}{'_norm' if normalize else ''}{'' if background else '_nobg'}"
 
 
 def output_paths(d, tag):
@@ -61,10 +75,10 @@ def output_paths(d, tag):
     return d / f'svm_pred{tag}.npy', d / f'svm_model{tag}.npz', d / f'svm_metrics{tag}.json'
 
 
-def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='sqrt', background=True):
+def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='sqrt', background=True, features='dino'):
     """The tag of a forest run's output files: rf_pred<tag>.npy, rf_model<tag>.npz, rf_metrics<tag>.json, rf_votes<tag>.npy."""
     mf = '' if max_features == 'sqrt' else '_all' if max_features == 'all' else f'_mf{max_features}'
-    return f"{num_samples}{sampling_mode}_rf{trees}{'' if max_depth is None else f'_d{max_depth}'}{mf}{'' if background else '_nobg'}"
+    return f"{num_samples}{sampling_mode}{FEATURE_TAGS[features]}_rf{trees}{'' if max_depth is None else f'_d{max_depth}'}{mf}{'' if background else '_nobg'}"
 
 
 def forest_paths(d, tag):
@@ -121,7 +135,7 @@ class _Svm:
         self.with_bg = with_bg
 
     def paths(self, d, num_samples, mode):
-        return output_paths(d, svm_tag(num_samples, mode, self.kernel, self.normalize, self.with_bg))
+        return output_paths(d, svm_tag(num_samples, mode, self.kernel, self.normalize, self.with_bg, self.args.features))
 
     def check_features(self, f, name):
         if self.kernel == 'rbf' and f > 768:
@@ -136,6 +150,9 @@ class _Svm:
 
     def predict(self, features, model, paths):
         return vt.svm.predict(features, model)
+
+    def predict_volume(self, volume, stats, channels, model, paths):
+        return vt.voxel_features.classify(volume, model, channels, stats)
 
     def describe(self, model):
         return f'{model.sv.shape[0]} support vectors ({model.n_support.tolist()} per class)'
@@ -181,9 +198,9 @@ class _Forest:
     def paths(self, d, num_samples, mode):
         a, m = self.args, self.model
         if m is not None:                                     # a loaded forest: what the file can tell
-            tag = forest_tag(num_samples, mode, m.trees, None, 'sqrt', self.with_bg)
+            tag = forest_tag(num_samples, mode, m.trees, None, 'sqrt', self.with_bg, a.features)
         else:
-            tag = forest_tag(num_samples, mode, a.trees, a.max_depth, self.max_features, self.with_bg)
+            tag = forest_tag(num_samples, mode, a.trees, a.max_depth, self.max_features, self.with_bg, a.features)
         return forest_paths(d, tag)
 
     def check_features(self, f, name):
@@ -204,6 +221,19 @@ class _Forest:
         wide = votes.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
         np.save(paths[3], (wide * 255 // (model.trees * 65535)).to(torch.uint8).cpu().numpy())
         return idx
+
+    def predict_volume(self, volume, stats, channels, model, paths):
+        if not self.args.votes:
+            return vt.voxel_features.classify(volume, model, channels, stats)
+        idx = torch.empty(volume.numel(), dtype=torch.uint8, device=volume.device)
+        # slab by slab: the uint32 votes of a whole volume (C x 537 MB at 512^3) never exist, only their uint8 shares
+        conf = np.empty((model.classes, volume.numel()), np.uint8)
+        for start, n, labels, votes in vt.voxel_features.slabs(volume, model, channels, stats, want_votes=True):
+            idx[start:start + n] = labels
+            wide = votes.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+            conf[:, start:start + n] = (wide * 255 // (model.trees * 65535)).to(torch.uint8).cpu().numpy()
+        np.save(paths[3], conf.reshape((model.classes,) + tuple(volume.shape)))
+        return idx.reshape(tuple(volume.shape))
 
     def describe(self, model):
         return f'{model.trees} trees, {model.n_nodes} nodes, depth {model.max_depth}'
@@ -230,6 +260,8 @@ def main(argv=None):
     parser.add_argument('--min-samples-leaf', type=int, default=1, help='forest: fewest training rows of a leaf')
     parser.add_argument('--no-bootstrap', action='store_true', help='forest: every tree sees every sample once')
     parser.add_argument('--votes', action='store_true', help='forest: also write the per-class vote shares rf_votes<tag>.npy')
+    parser.add_argument('--features', type=str, choices=list(FEATURE_TAGS), default='dino',
+                        help='dino (default): the feature file; handcrafted: 11 channels computed from the volume itself; intensity: its intensity alone')
     parser.add_argument('--model', type=str, default=None, metavar='FILE', help='apply this saved model instead of fitting')
     parser.add_argument('--seed', type=int, default=0, help='seed of the sample draws')
     parser.add_argument('--overwrite', action='store_true', help='replace existing output files')
@@ -240,6 +272,9 @@ def main(argv=None):
         _fail('data', f'{d} is not a directory')
     if not args.num_samples >= 0:
         _fail('num-samples', f'{args.num_samples} is negative')
+    own = args.features != 'dino'                             # the features come from the volume itself
+    if own and args.normalize:
+        _fail('normalize', f'does not apply to --features {args.features}: the channels are standardised, not directions')
     model = None
     kind = args.classifier
     if args.model:
@@ -253,6 +288,12 @@ def main(argv=None):
             model = clf.model = clf.module.load_model(args.model)
         except (OSError, ValueError, KeyError) as e:
             _fail('model', e)
+    if own and model is not None:
+        f_model = model.n_features if kind == 'forest' else model.sv.shape[1]
+        if f_model != 32:
+            _fail('model', f'fitted on F = {f_model} features, --features {args.features} gives F = 32 (its rows in a zeroed 32-row matrix)')
+        if kind != 'forest' and model.normalize:
+            _fail('model', f'fitted with --normalize, which --features {args.features} refuses')
     has_labels = (d / 'labels.npy').exists()
     background = args.background
     if background == 'auto':
@@ -276,19 +317,32 @@ def main(argv=None):
         sys.exit(0)
     if not (d / 'volume.npy').exists():
         _fail('data', f'{d} has no volume.npy')
-    feat_fn = find_feature_file(d)
-    if feat_fn is None:
+    feat_fn = None if own else find_feature_file(d)
+    if feat_fn is None and not own:
         _fail('data', f'No features found in {d}')
     print(f'Inferring for {d} using sampling mode {mode} and {args.num_samples} samples')
 
     volume = np.flip(np.load(d / 'volume.npy', allow_pickle=True), axis=-3)
     vol_shape = tuple(int(s) for s in np.squeeze(volume).shape[-3:])
     labels = np.flip(np.load(d / 'labels.npy', allow_pickle=True)[()], axis=-3).copy() if has_labels else None
-    features = pick_features(np.load(feat_fn, allow_pickle=True)[()])
-    f = int(features.shape[0])
-    if features.ndim != 4 or f % 32 or not 32 <= f <= 1024:
-        _fail('data', f'{feat_fn.name} holds {tuple(features.shape)}: F = {f} is not a multiple of 32 in 32..1024')
-    clf.check_features(f, feat_fn.name)
+    if own:
+        try:
+            vt.voxel_features.check_shape(np.squeeze(volume).shape)
+        except ValueError as e:
+            _fail('features', f'volume.npy: {e}')
+        channels = vt.voxel_features.CHANNELS if args.features == 'handcrafted' else 1
+        clf.check_features(32, f'--features {args.features}')
+        try:
+            vol_dev = vt.voxel_features._volume(np.ascontiguousarray(np.squeeze(volume), dtype=np.float32))
+            vstats = vt.voxel_features.stats(vol_dev)
+        except ValueError as e:
+            _fail('features', f'volume.npy: {e}')
+    else:
+        features = pick_features(np.load(feat_fn, allow_pickle=True)[()])
+        f = int(features.shape[0])
+        if features.ndim != 4 or f % 32 or not 32 <= f <= 1024:
+            _fail('data', f'{feat_fn.name} holds {tuple(features.shape)}: F = {f} is not a multiple of 32 in 32..1024')
+        clf.check_features(f, feat_fn.name)
 
     torch.manual_seed(args.seed)
     t0 = time.time()
@@ -321,14 +375,20 @@ def main(argv=None):
                 values.append(0)
         if len(values) < 2 or len(values) > vt._lib.SVM_MAX_CLASSES:
             _fail('data', f'{len(values)} classes (background included): the classifier takes 2..{vt._lib.SVM_MAX_CLASSES}')
-        samples, targets = vt.svm.sample(features, annotations, vol_shape, args.normalize)
+        if own:
+            try:
+                samples, targets = vt.voxel_features.sample(vol_dev, annotations, vstats, channels)
+            except ValueError as e:
+                _fail('data', e)
+        else:
+            samples, targets = vt.svm.sample(features, annotations, vol_shape, args.normalize)
         order = np.argsort(values)                                         # class names in ascending label value
         try:
             model = clf.fit(samples, np.asarray(values)[targets], [list(annotations)[i] for i in order])
         except ValueError as e:
             _fail('num-samples', e)
     t1 = time.time()
-    pred_idx = clf.predict(features, model, paths)
+    pred_idx = clf.predict_volume(vol_dev, vstats, channels, model, paths) if own else clf.predict(features, model, paths)
     pred = torch.from_numpy(model.labels).to(pred_idx.device)[pred_idx.long()].contiguous()
     torch.cuda.synchronize()
     t2 = time.time()

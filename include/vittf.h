@@ -583,6 +583,41 @@ int vittf_forest_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uin
                         const uint32_t* tree_offset, int32_t trees, int32_t classes, int32_t max_depth, uint8_t* labels,
                         uint32_t* votes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Hand-crafted voxel features (vit-tf_amd/voxel_features.py, classify_features.py --features handcrafted | intensity): the
+ * 11-channel per-voxel vector of the reference's classical baseline (predict_svm_rf.py:25-65) at the volume's own
+ * resolution, as rows of the fp16 [f][nvox] matrix the two decision passes above take.
+ * vol: fp32 (n0, n1, n2), C-contiguous, 4-byte aligned; every dimension in 2..2048 and n0 n1 n2 < 2^31; vmax its maximum
+ * (vittf_volume_minmax), finite and > 0.  With I = vol / vmax and v = (i0 n1 + i1) n2 + i2 the raw channels are
+ *   0      I
+ *   1      sqrt(gx^2 + gy^2 + gz^2), g = 0.5 (I[+1] - I[-1]) along each axis; a neighbour outside the volume counts as 0
+ *   2..7   I at (i0+1), (i1+1), (i2+1), (i0-1), (i1-1), (i2-1); a neighbour outside the volume is the border voxel itself
+ *   8..10  i0 / n0 - 0.5, i1 / n1 - 0.5, i2 / n2 - 0.5
+ * and each is standardised over the whole volume, (x - mean_c) / std_c, std_c the unbiased one (divisor nvox - 1).
+ *
+ * vittf_voxel_feature_stats: stats (device fp64 [2][11], 8-byte aligned) = the means, then the stds of the raw channels,
+ * accumulated in fp64 over workgroups of 16384 consecutive voxels whose partial sums (ws: 8-byte aligned, at least
+ * vittf_voxel_feature_stats_workspace_bytes(n0, n1, n2) = 128 bytes per workgroup; 0 for a shape the call refuses; too small:
+ * VITTF_ERR_WORKSPACE) are added in a fixed order by a second launch: no floating-point atomics, the same call gives the same
+ * bytes.  The coordinate channels take their closed forms.
+ *
+ * vittf_voxel_features: out[c out_stride + i] (fp16 bits, 2-byte aligned, out_stride >= n) = the standardised channel
+ * c < channels of voxel voxel_index[i] (device int64 [n], 8-byte aligned, every entry in 0..nvox-1: the CALLER checks them;
+ * the kernel writes NaN for one that is not) or, with voxel_index NULL, of voxel v0 + i (0 <= v0, v0 + n <= nvox), for
+ * i < n, n >= 1.  channels is 11 or 1 (the intensity alone); rows from `channels` up are neither read nor written -- the
+ * caller embeds the rows in a zeroed 32-row matrix for the decision passes.  A voxel's bits do not depend on the addressing
+ * mode, on v0, n or out_stride.  16-byte stores where out + c out_stride + i is 16-byte aligned (every row when out_stride
+ * is a multiple of 8), 2-byte stores elsewhere.  The call reads `stats` back (it waits for the stream) and returns
+ * VITTF_ERR_INVALID_ARG without a launch when a mean is not finite or a std of a channel < channels is 0 or not finite.
+ * fp32 arithmetic from coefficients folded in fp64: I = vol (1 / vmax), then one fma per channel.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_VOXFEAT_CHANNELS 11
+size_t vittf_voxel_feature_stats_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int vittf_voxel_feature_stats(const float* vol, int32_t n0, int32_t n1, int32_t n2, float vmax, double* stats, void* ws,
+                              size_t ws_bytes, void* stream);
+int vittf_voxel_features(const float* vol, int32_t n0, int32_t n1, int32_t n2, float vmax, const double* stats, int32_t channels,
+                         const int64_t* voxel_index, int64_t v0, int64_t n, uint16_t* out, int64_t out_stride, void* stream);
+
 /* ---- label-volume helpers: sampler candidate masks and scores --------------------------- */
 /* dst = binary_erosion(set, generate_binary_structure(3, connectivity)) with scipy.ndimage's defaults (one iteration,
  * border_value 0): set = {src == class_id} (class_id 0..255) or {src != 0} (class_id < 0); uint8 volumes (n0, n1, n2),
