@@ -16,7 +16,8 @@
 // Bistochastisation and the CG are one launch per phase over all vertices (fp64; per-workgroup tree reductions whose
 // partials every workgroup then adds in the same fixed order, so dot products are deterministic; convergence latched
 // in a device flag, no host round trip).  All arithmetic that the reference does in fp64 is fp64 here;
-// the fp32 parts (resize, Sobel) use unfused multiply / add in the CPU operators' order.
+// the fp32 parts follow the CPU operators' order: the Sobel sum unfused (sum_squares_unfused), the resize with the
+// fused source index and blends that the compiler may contract (lin_coord, trilinear_kernel; fewer roundings, not more).
 #include "vittf_internal.h"
 
 #include <math.h>
@@ -28,7 +29,10 @@ constexpr int BT = 256;
 
 // ---- F.interpolate(mode='trilinear', align_corners=False), fp32 ------------------------------------------------
 __device__ __forceinline__ void lin_coord(int o, float scale, int in_size, int& i0, int& i1, float& w0, float& w1) {
-  float src = __fsub_rn(__fmul_rn(scale, (float)o + 0.5f), 0.5f);   // area_pixel_compute_source_index
+  // area_pixel_compute_source_index: scale * (o + 0.5) - 0.5 rounded once, as the contracting builds of the operator do
+  // (AVX2 / AVX-512 CPU kernels, CUDA).  Written as __fsub_rn(__fmul_rn(..)) it compiled to this very instruction
+  // (see sum_squares_unfused below); spelled out, it no longer depends on the compiler's choice.
+  float src = fmaf(scale, (float)o + 0.5f, -0.5f);
   if (src < 0.f) src = 0.f;
   i0 = (int)src;
   if (i0 > in_size - 1) i0 = in_size - 1;
@@ -98,6 +102,16 @@ __global__ __launch_bounds__(BT) void bbox_kernel(const float* __restrict__ sim,
 
 struct Box { int lo0, lo1, lo2, c0, c1, c2, d1, d2; };   // crop origin / extent inside a (., d1, d2) volume
 
+// (dx^2 + dy^2) + dz^2 with every product rounded before it is added, as torch's one-operator-per-step Sobel does.
+// HIP's __fmul_rn / __fadd_rn are plain `*` and `+`: once inlined, hipcc contracts them like any other expression, and
+// the last square used to go into the sum unrounded (v_fmac_f32) -- a Sobel magnitude one spacing off at some voxels,
+// up to two fp32 spacings in the refined map (tests/test_gpu_bilateral.py).  The pragma takes the contraction away.
+__device__ __forceinline__ float sum_squares_unfused(float dx, float dy, float dz) {
+#pragma clang fp contract(off)
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  return (xx + yy) + zz;
+}
+
 // Sobel magnitude of ref / 255 inside the crop (zero padding at the crop faces), fp32, the three squares added in the
 // reference's order (last dim first); also the maximum (as float bits: the values are >= 0)
 __global__ __launch_bounds__(BT) void sobel_kernel(const unsigned char* __restrict__ ref, Box b, float* __restrict__ g,
@@ -115,7 +129,7 @@ __global__ __launch_bounds__(BT) void sobel_kernel(const unsigned char* __restri
     const float dx = diff(at(z, y, x + 1), at(z, y, x - 1));
     const float dy = diff(at(z, y + 1, x), at(z, y - 1, x));
     const float dz = diff(at(z + 1, y, x), at(z - 1, y, x));
-    val = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    val = sqrtf(sum_squares_unfused(dx, dy, dz));
     g[idx] = val;
   }
   // block maximum -> one atomic
