@@ -1,9 +1,10 @@
 """Support-vector or random-forest classification of a feature volume from annotated voxels: a learned label volume.
 
-    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest}]
+    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest,mlp}]
                                 [--kernel {rbf,linear}] [--C 1.0] [--gamma scale|FLOAT] [--normalize] [--tol T]
                                 [--trees 256] [--max-depth N] [--max-features sqrt|all|INT|FRACTION] [--min-samples-leaf 1]
                                 [--no-bootstrap] [--votes] [--features {dino,handcrafted,intensity}]
+                                [--hidden W1[,W2]] [--epochs 100] [--batch 256] [--lr 1e-3] [--weight-decay 1e-2] [--probs]
                                 [--background {auto,labels,border,none}] [--model FILE] [--seed S] [--overwrite]
 
 DIR follows predict_ntf.py's directory contract: ``volume.npy`` and ``labels.npy`` (flipped on axis -3), the largest file
@@ -34,6 +35,19 @@ by the file.  Outputs, with the tag ``<num><mode>_rf<trees>[_d<depth>][_all|_mf<
     in the place of n_sv): as the SVM's;
   * with ``--votes``, ``rf_votes<tag>.npy``: uint8 (C, W', H', D'), votes * 255 // (trees * 65535) per class in the order of the
     model's classes (ascending label value) -- a confidence volume for thresholds or the bilateral solver.
+
+``--classifier mlp`` trains an MLP head instead (vt.mlp.fit: numpy fp64 on the host, softmax cross-entropy, AdamW, cosine
+schedule; the pass over the volume is libvittf's vittf_mlp_decide, mlp.hip) on the same samples, background class and seed:
+the reference's old/compare_feat_sampling_mlp.py.  ``--hidden ""`` (the default) is the linear probe, ``--hidden 32,64`` two
+hidden layers (at most two, multiples of 32 in 32..256).  ``--normalize`` gives the reference's cosine geometry (with
+``--features dino`` only); ``--kernel``, ``--C``, ``--gamma`` and ``--tol`` given explicitly are refused.  The label is the
+plain arg-max of the logits (the reference's ``sigmoid(max logit) > 0.5 else 0`` rule is not reproduced).  Outputs, with the
+tag ``<num><mode>[_hand|_intensity]_mlp[<w1>[x<w2>]][_norm][_nobg]``:
+  * ``mlp_pred<tag>.npy``, ``mlp_model<tag>.npz`` (vt.mlp.save_model), ``mlp_metrics<tag>.json`` (n_params, hidden, final_loss and
+    train_accuracy in the place of n_sv): as the SVM's;
+  * with ``--probs``, ``mlp_probs<tag>.npy``: uint8 (C, W', H', D'), floor(255 softmax + 0.5) per class in the order of the
+    model's classes (ascending label value) -- calibrated probability volumes for transfer functions, label_islands.py or the
+    bilateral solver.
 
 ``--features handcrafted`` classifies the VOLUME ITSELF instead of a feature file: the reference baseline's default mode
 (predict_svm_rf.py:25-65), an 11-channel vector per voxel at the volume's full resolution -- intensity, gradient magnitude, the
@@ -84,6 +98,17 @@ def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='
 def forest_paths(d, tag):
     d = Path(d)
     return d / f'rf_pred{tag}.npy', d / f'rf_model{tag}.npz', d / f'rf_metrics{tag}.json', d / f'rf_votes{tag}.npy'
+
+
+def mlp_tag(num_samples, sampling_mode, hidden=(), normalize=False, background=True, features='dino'):
+    """The tag of an MLP run's output files: mlp_pred<tag>.npy, mlp_model<tag>.npz, mlp_metrics<tag>.json, mlp_probs<tag>.npy."""
+    return (f"{num_samples}{sampling_mode}{FEATURE_TAGS[features]}_mlp{'x'.join(str(w) for w in hidden)}"
+            f"{'_norm' if normalize else ''}{'' if background else '_nobg'}")
+
+
+def mlp_paths(d, tag):
+    d = Path(d)
+    return d / f'mlp_pred{tag}.npy', d / f'mlp_model{tag}.npz', d / f'mlp_metrics{tag}.json', d / f'mlp_probs{tag}.npy'
 
 
 def find_feature_file(d):
@@ -242,12 +267,80 @@ class _Forest:
         return {'n_trees': model.trees, 'n_nodes': model.n_nodes, 'max_depth': model.max_depth}
 
 
+class _Mlp:
+    """The MLP-head side of main."""
+    name, module = 'MLP', vt.mlp
+
+    def __init__(self, args):
+        self.args, self.model = args, None
+        for k in SVM_DEFAULTS:
+            if getattr(args, k) is not None:
+                _fail(k, 'does not apply to --classifier mlp')
+        try:
+            self.hidden = vt.mlp.parse_hidden(args.hidden)
+        except ValueError:
+            _fail('hidden', f'{args.hidden!r} is not a comma-separated list of widths')
+        L = vt._lib
+        if len(self.hidden) > L.MLP_MAX_LAYERS or any(w % 32 or not 32 <= w <= L.MLP_MAX_WIDTH for w in self.hidden):
+            _fail('hidden', f'{args.hidden!r}: at most {L.MLP_MAX_LAYERS} widths, multiples of 32 in 32..{L.MLP_MAX_WIDTH}')
+        if args.epochs < 1:
+            _fail('epochs', f'{args.epochs} is not positive')
+        if args.batch < 1:
+            _fail('batch', f'{args.batch} is not positive')
+        if not (args.lr > 0 and np.isfinite(args.lr)):
+            _fail('lr', f'{args.lr} is not a positive number')
+        if not (args.weight_decay >= 0 and np.isfinite(args.weight_decay)):
+            _fail('weight-decay', f'{args.weight_decay} is negative or not finite')
+
+    def configure(self, with_bg):
+        m = self.model
+        self.hidden, self.normalize = (self.hidden, self.args.normalize) if m is None else (m.hidden, m.normalize)
+        self.with_bg = with_bg
+
+    def paths(self, d, num_samples, mode):
+        return mlp_paths(d, mlp_tag(num_samples, mode, self.hidden, self.normalize, self.with_bg, self.args.features))
+
+    def check_features(self, f, name):
+        if self.model is not None and self.model.n_features != f:
+            _fail('model', f'fitted on F = {self.model.n_features} features, {name} has F = {f}')
+
+    def fit(self, samples, targets, names):
+        a = self.args
+        return vt.mlp.fit(samples, targets, hidden=self.hidden, epochs=a.epochs, batch=a.batch, lr=a.lr, weight_decay=a.weight_decay,
+                          seed=a.seed, normalize=self.normalize, class_names=names)
+
+    def predict(self, features, model, paths):
+        if not self.args.probs:
+            return vt.mlp.predict(features, model)
+        idx, probs = vt.mlp.predict(features, model, return_probs=True)
+        np.save(paths[3], probs.cpu().numpy())
+        return idx
+
+    def predict_volume(self, volume, stats, channels, model, paths):
+        if not self.args.probs:
+            return vt.voxel_features.classify(volume, model, channels, stats)
+        idx = torch.empty(volume.numel(), dtype=torch.uint8, device=volume.device)
+        conf = np.empty((model.classes, volume.numel()), np.uint8)               # slab by slab, as the forest's votes
+        for start, n, labels, probs in vt.voxel_features.slabs(volume, model, channels, stats, want_votes=True):
+            idx[start:start + n] = labels
+            conf[:, start:start + n] = probs.cpu().numpy()
+        np.save(paths[3], conf.reshape((model.classes,) + tuple(volume.shape)))
+        return idx.reshape(tuple(volume.shape))
+
+    def describe(self, model):
+        return f'hidden {list(model.hidden)}, {model.n_params} parameters, training accuracy {model.train_accuracy:.4f}'
+
+    def metrics(self, model):
+        return {'n_params': model.n_params, 'hidden': list(model.hidden), 'final_loss': model.final_loss,
+                'train_accuracy': model.train_accuracy}
+
+
 def main(argv=None):
     parser = ArgumentParser('Classify a feature volume with a support-vector machine or a random forest trained on annotated voxels')
     parser.add_argument('--data', type=str, required=True, help='directory holding volume, features and annotations / labels')
     parser.add_argument('--num-samples', type=float, default=0.0, help='annotations sampled per class from the labels (0: use the annotation file)')
     parser.add_argument('--sampling-mode', type=str, choices=['uniform', 'surface', 'both'], default='both', help='where samples are drawn from')
-    parser.add_argument('--classifier', type=str, choices=['svm', 'forest'], default=None, help='svm (the default) or forest; --model FILE implies it')
+    parser.add_argument('--classifier', type=str, choices=['svm', 'forest', 'mlp'], default=None, help='svm (the default), forest or mlp; --model FILE implies it')
     parser.add_argument('--kernel', type=str, choices=list(vt.svm.KERNELS), default=None, help='svm: rbf (default) or linear')
     parser.add_argument('--C', type=float, default=None, help='svm: box constraint of the C-SVC (default 1.0)')
     parser.add_argument('--gamma', type=str, default=None, help="svm: RBF width: 'scale' (1 / (F var(samples)), default) or a number")
@@ -260,6 +353,12 @@ def main(argv=None):
     parser.add_argument('--min-samples-leaf', type=int, default=1, help='forest: fewest training rows of a leaf')
     parser.add_argument('--no-bootstrap', action='store_true', help='forest: every tree sees every sample once')
     parser.add_argument('--votes', action='store_true', help='forest: also write the per-class vote shares rf_votes<tag>.npy')
+    parser.add_argument('--hidden', type=str, default='', metavar='W1[,W2]', help='mlp: hidden widths, comma-separated (default: none, a linear probe)')
+    parser.add_argument('--epochs', type=int, default=100, help='mlp: passes over the samples')
+    parser.add_argument('--batch', type=int, default=256, help='mlp: samples per step')
+    parser.add_argument('--lr', type=float, default=1e-3, help='mlp: initial learning rate of the cosine schedule')
+    parser.add_argument('--weight-decay', type=float, default=1e-2, help="mlp: AdamW's decoupled weight decay")
+    parser.add_argument('--probs', action='store_true', help='mlp: also write the per-class probabilities mlp_probs<tag>.npy')
     parser.add_argument('--features', type=str, choices=list(FEATURE_TAGS), default='dino',
                         help='dino (default): the feature file; handcrafted: 11 channels computed from the volume itself; intensity: its intensity alone')
     parser.add_argument('--model', type=str, default=None, metavar='FILE', help='apply this saved model instead of fitting')
@@ -278,18 +377,18 @@ def main(argv=None):
     model = None
     kind = args.classifier
     if args.model:
-        of_file = 'forest' if vt.forest.is_forest_file(args.model) else 'svm'
+        of_file = 'mlp' if vt.mlp.is_mlp_file(args.model) else 'forest' if vt.forest.is_forest_file(args.model) else 'svm'
         if kind is not None and kind != of_file:
             _fail('model', f'{args.model} does not hold a {kind} model')
         kind = of_file
-    clf = (_Forest if kind == 'forest' else _Svm)(args)       # the classifier's own argument checks come first
+    clf = {'forest': _Forest, 'mlp': _Mlp}.get(kind, _Svm)(args)       # the classifier's own argument checks come first
     if args.model:
         try:
             model = clf.model = clf.module.load_model(args.model)
         except (OSError, ValueError, KeyError) as e:
             _fail('model', e)
     if own and model is not None:
-        f_model = model.n_features if kind == 'forest' else model.sv.shape[1]
+        f_model = model.sv.shape[1] if kind in (None, 'svm') else model.n_features
         if f_model != 32:
             _fail('model', f'fitted on F = {f_model} features, --features {args.features} gives F = 32 (its rows in a zeroed 32-row matrix)')
         if kind != 'forest' and model.normalize:

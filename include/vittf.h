@@ -584,6 +584,35 @@ int vittf_forest_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uin
                         uint32_t* votes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MLP head over a feature volume (vit-tf_amd/mlp.py, classify_features.py --classifier mlp): the decision pass of the
+ * reference's old/compare_feat_sampling_mlp.py head, Linear (-> ReLU -> Linear) x layers, over every voxel.
+ * feat, nvox, voxel_norm: as for the SVM entries above (fp16 [f][nvox], f a multiple of 32 in 32..1024; with voxel_norm the
+ * voxel is x / norm, applied to the first contraction before its bias).  widths [host]: the `layers` hidden widths
+ * (layers in 0..VITTF_MLP_MAX_LAYERS, may be NULL for 0), each a multiple of 32 in 32..VITTF_MLP_MAX_WIDTH; classes in
+ * 2..VITTF_MLP_MAX_CLASSES.  weights: the layers + 1 matrices fp32 [out][in] one behind the other (in = f, then the widths;
+ * the last out = classes), biases: their fp32 [out] vectors one behind the other; all values finite.
+ * labels uint8 [nvox]: the arg-max of the fp32 logits, the lowest index among equal logits.  logits NULL or fp32
+ * [classes][nvox]; probs NULL or uint8 [classes][nvox] = floor(255 softmax_c + 0.5), the maximum subtracted first, from the
+ * same registers.  The labels are the same bytes whatever else is asked for.
+ * Arithmetic: every matrix is scaled by a power of two (largest entry into [2^10, 2^11)) and split into fp16 hi + lo
+ * (2^-22 relative, 2^-35 of the largest entry absolute); the voxels' fp16 features are exact MFMA operands; fp32
+ * accumulation in a fixed order, no atomics: the same call gives the same bytes.  After bias and ReLU the accumulator tile
+ * of a wave is the B operand of the next contraction as it lies (hi + lo; hi hi + hi lo + lo hi), scaled PER VOXEL by a
+ * power of two that brings the voxel's largest activation into [2^10, 2^11): the hand-over cannot leave the fp16 range
+ * whatever the activations are.  Hidden activations never leave the chip; the volume is read once.
+ * Three launches (scales, weight images, decision).  ws: 16-byte aligned, >= vittf_mlp_workspace_bytes(f, widths, layers,
+ * classes) = 256 + sum over the matrices of (in / 32) x ceil(out / 32) x 5120 bytes (0 for a head the call refuses); too
+ * small: VITTF_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_MLP_MAX_CLASSES 8   /* most classes of one head: the logits of a voxel are 8 rows of one MFMA tile */
+#define VITTF_MLP_MAX_LAYERS 2    /* most hidden layers */
+#define VITTF_MLP_MAX_WIDTH 256   /* widest hidden layer: 8 accumulator tiles a wave */
+size_t vittf_mlp_workspace_bytes(int32_t f, const int32_t* widths, int32_t layers, int32_t classes);
+int vittf_mlp_decide(const uint16_t* feat, int32_t f, int64_t nvox, const float* weights, const float* biases,
+                     const int32_t* widths, int32_t layers, int32_t classes, const float* voxel_norm, uint8_t* labels,
+                     float* logits, uint8_t* probs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hand-crafted voxel features (vit-tf_amd/voxel_features.py, classify_features.py --features handcrafted | intensity): the
  * 11-channel per-voxel vector of the reference's classical baseline (predict_svm_rf.py:25-65) at the volume's own
  * resolution, as rows of the fp16 [f][nvox] matrix the two decision passes above take.

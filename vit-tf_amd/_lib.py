@@ -122,6 +122,8 @@ SIGNATURES = {
     'vittf_svm_rbf_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_svm_linear_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     'vittf_forest_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'vittf_mlp_workspace_bytes': (_sz, [_i32, _P(_i32), _i32, _i32]),
+    'vittf_mlp_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _P(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_voxel_feature_stats_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'vittf_voxel_feature_stats': (C.c_int, [_vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _sz, _vp]),
     'vittf_voxel_features': (C.c_int, [_vp, _i32, _i32, _i32, C.c_float, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -182,6 +184,9 @@ FOREST_MAX_CLASSES = 8    # VITTF_FOREST_MAX_CLASSES: classes of one vittf_fores
 FOREST_MAX_TREES = 4096   # VITTF_FOREST_MAX_TREES: trees of one model (4096 x 65535 < 2^32: the uint32 votes cannot overflow)
 FOREST_MAX_NODES = 65535  # VITTF_FOREST_MAX_NODES: nodes of one tree (16-bit child indices)
 FOREST_MAX_DEPTH = 64     # VITTF_FOREST_MAX_DEPTH: the deepest tree vittf_forest_decide walks
+MLP_MAX_CLASSES = 8       # VITTF_MLP_MAX_CLASSES: classes of one vittf_mlp_decide head
+MLP_MAX_LAYERS = 2        # VITTF_MLP_MAX_LAYERS: hidden layers of one head
+MLP_MAX_WIDTH = 256       # VITTF_MLP_MAX_WIDTH: the widest hidden layer (a multiple of 32 from 32 up)
 VOXFEAT_CHANNELS = 11     # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
 KMEANS_SPANS = 128       # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 

@@ -172,18 +172,19 @@ def sample(volume, annotations, stats, channels=CHANNELS, pad_to=32):
 
 def slabs(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, want_votes=False):
     """Generator over contiguous voxel ranges: (start, n, labels uint8 [n], votes) of each, the device tensors one decision
-    call left (votes: vt.forest.decide's uint32 [C][n] or vt.svm.decide's fp32 decisions [P][n]; None unless want_votes).
+    call left (votes: vt.forest.decide's uint32 [C][n], vt.svm.decide's fp32 decisions [P][n] or vt.mlp.decide's uint8
+    probabilities [C][n]; None unless want_votes).
     The ranges start at multiples of 8 and share one [32][slab] buffer.  ``classify`` is built on it."""
-    from . import forest, svm
+    from . import forest, mlp, svm
     lib = _lib.require_device()
     _check_channels(channels)
     vol = _volume(volume)
     st = _volume_stats(vol) if stats is None else stats
     _check_stats(st, channels)
-    is_forest = isinstance(model, forest.ForestModel)
-    if not is_forest and not isinstance(model, svm.SvmModel):
-        raise ValueError(f'model must be a ForestModel or an SvmModel, got {type(model).__name__}')
-    f = model.n_features if is_forest else model.sv.shape[1]
+    is_forest, is_mlp = isinstance(model, forest.ForestModel), isinstance(model, mlp.MlpModel)
+    if not is_forest and not is_mlp and not isinstance(model, svm.SvmModel):
+        raise ValueError(f'model must be a ForestModel, an SvmModel or an MlpModel, got {type(model).__name__}')
+    f = model.n_features if is_forest or is_mlp else model.sv.shape[1]
     if f != 32:
         raise ValueError(f'the model was fitted on F = {f} features, the hand-crafted features have F = 32')
     if not is_forest and model.normalize:
@@ -203,7 +204,10 @@ def slabs(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, wan
             if n != slab:
                 x.zero_()                                           # the rows lie elsewhere in the buffer now
             _compose_into(lib, vol, st, st_dev, channels, None, start, n, x)
-            labels, votes = (forest.decide(x, model, want_votes) if is_forest else svm.decide(x, model, None, want_votes))
+            if is_mlp:
+                labels, _, votes = mlp.decide(x, model, None, False, want_votes)
+            else:
+                labels, votes = (forest.decide(x, model, want_votes) if is_forest else svm.decide(x, model, None, want_votes))
             yield start, n, labels, votes
 
 
@@ -211,17 +215,17 @@ def classify(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, 
     """uint8 device volume of class INDICES 0..C-1 (model.labels[index] is the value a label volume carries): the model's
     decision for every voxel's hand-crafted features, slab by slab (slab_voxels voxels at a time, a multiple of 8: one
     reusable [32][slab] buffer, 1 GiB at the default) -- byte for byte what one decide call on compose()'s whole matrix gives.
-    model: a ForestModel or an SvmModel with F = 32.  With want_votes also the forest's uint32 votes or the machine's fp32
-    decisions, [C or P] + the volume's shape."""
+    model: a ForestModel, an SvmModel or an MlpModel with F = 32.  With want_votes also the forest's uint32 votes, the
+    machine's fp32 decisions or the head's uint8 probabilities, [C or P] + the volume's shape."""
     vol = _volume(volume)
     out = torch.empty(vol.numel(), dtype=torch.uint8, device=vol.device)
     votes = None
     for start, n, labels, v in slabs(vol, model, channels, stats, slab_voxels, want_votes):
         out[start:start + n] = labels
         if want_votes:
-            bits = v.view(torch.int32)                              # (uint32 votes: copied as their bits)
+            bits = v if v.dtype == torch.uint8 else v.view(torch.int32)     # (uint32 votes: copied as their bits)
             if votes is None:
-                votes, dtype = torch.empty((v.shape[0], vol.numel()), dtype=torch.int32, device=vol.device), v.dtype
+                votes, dtype = torch.empty((v.shape[0], vol.numel()), dtype=bits.dtype, device=vol.device), v.dtype
             votes[:, start:start + n] = bits
     out = out.reshape(tuple(vol.shape))
     if want_votes:
