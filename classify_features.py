@@ -1,10 +1,12 @@
-"""Support-vector or random-forest classification of a feature volume from annotated voxels: a learned label volume.
+"""Support-vector, random-forest, MLP-head or k-nearest-neighbour classification of a feature volume from annotated voxels: a
+learned label volume.
 
-    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest,mlp}]
+    python classify_features.py --data DIR [--num-samples N] [--sampling-mode {uniform,surface,both}] [--classifier {svm,forest,mlp,knn}]
                                 [--kernel {rbf,linear}] [--C 1.0] [--gamma scale|FLOAT] [--normalize] [--tol T]
                                 [--trees 256] [--max-depth N] [--max-features sqrt|all|INT|FRACTION] [--min-samples-leaf 1]
                                 [--no-bootstrap] [--votes] [--features {dino,handcrafted,intensity}]
                                 [--hidden W1[,W2]] [--epochs 100] [--batch 256] [--lr 1e-3] [--weight-decay 1e-2] [--probs]
+                                [--k 20] [--temperature 0.07] [--knn-weights {softmax,uniform}]
                                 [--background {auto,labels,border,none}] [--model FILE] [--seed S] [--overwrite]
 
 DIR follows predict_ntf.py's directory contract: ``volume.npy`` and ``labels.npy`` (flipped on axis -3), the largest file
@@ -48,6 +50,21 @@ tag ``<num><mode>[_hand|_intensity]_mlp[<w1>[x<w2>]][_norm][_nobg]``:
   * with ``--probs``, ``mlp_probs<tag>.npy``: uint8 (C, W', H', D'), floor(255 softmax + 0.5) per class in the order of the
     model's classes (ascending label value) -- calibrated probability volumes for transfer functions, label_islands.py or the
     bilateral solver.
+
+``--classifier knn`` is the weighted k-nearest-neighbour classifier of the DINO evaluation protocol (vt.knn; the pass over the
+volume is libvittf's vittf_knn_decide, knn.hip) on the same samples, background class and seed.  It has NO fit: the model is the
+bank of annotated samples itself (L2-normalised, rounded once to fp16), so fit_time is the sampling and the rounding only.
+Every voxel is compared with every bank sample by cosine similarity; the ``--k`` (1..32, default 20) nearest vote with weights
+exp(sim / T) (``--temperature``, default 0.07) or 1 (``--knn-weights uniform``); the label is the arg-max of the per-class sums.
+The geometry is always cosine: ``--normalize`` is implied, is accepted and changes nothing, and is not in the tag.  ``--kernel``,
+``--C``, ``--gamma``, ``--tol`` given explicitly are refused, and so are ``--votes`` and ``--features handcrafted|intensity``
+(cosine distance on standardised channels is not the baseline anyone means; a Euclidean metric is not built).  F <= 768, as for
+the RBF machine.  Outputs, with the tag ``<num><mode>_knn<k>[_t<T>][_uni][_nobg]`` (``_t<T>`` only when T is not 0.07, ``_uni``
+for uniform weights):
+  * ``knn_pred<tag>.npy``, ``knn_model<tag>.npz`` (vt.knn.save_model), ``knn_metrics<tag>.json`` (n_bank, k, temperature and
+    weights in the place of n_sv): as the SVM's;
+  * with ``--probs``, ``knn_probs<tag>.npy``: uint8 (C, W', H', D'), floor(255 score_c / sum_c score + 0.5) per class in the order
+    of the model's classes (ascending label value).
 
 ``--features handcrafted`` classifies the VOLUME ITSELF instead of a feature file: the reference baseline's default mode
 (predict_svm_rf.py:25-65), an 11-channel vector per voxel at the volume's full resolution -- intensity, gradient magnitude, the
@@ -109,6 +126,17 @@ def mlp_tag(num_samples, sampling_mode, hidden=(), normalize=False, background=T
 def mlp_paths(d, tag):
     d = Path(d)
     return d / f'mlp_pred{tag}.npy', d / f'mlp_model{tag}.npz', d / f'mlp_metrics{tag}.json', d / f'mlp_probs{tag}.npy'
+
+
+def knn_tag(num_samples, sampling_mode, k=20, temperature=0.07, weights='softmax', background=True):
+    """The tag of a k-NN run's output files: knn_pred<tag>.npy, knn_model<tag>.npz, knn_metrics<tag>.json, knn_probs<tag>.npy."""
+    return (f"{num_samples}{sampling_mode}_knn{k}{'' if temperature == 0.07 else f'_t{temperature:g}'}"
+            f"{'_uni' if weights == 'uniform' else ''}{'' if background else '_nobg'}")
+
+
+def knn_paths(d, tag):
+    d = Path(d)
+    return d / f'knn_pred{tag}.npy', d / f'knn_model{tag}.npz', d / f'knn_metrics{tag}.json', d / f'knn_probs{tag}.npy'
 
 
 def find_feature_file(d):
@@ -335,12 +363,64 @@ class _Mlp:
                 'train_accuracy': model.train_accuracy}
 
 
+class _Knn:
+    """The k-nearest-neighbour side of main."""
+    name, module = 'KNN', vt.knn
+
+    def __init__(self, args):
+        self.args, self.model = args, None
+        for k in SVM_DEFAULTS:
+            if getattr(args, k) is not None:
+                _fail(k, 'does not apply to --classifier knn')
+        if args.votes:
+            _fail('votes', 'does not apply to --classifier knn (--probs writes its per-class shares)')
+        if args.features != 'dino':
+            _fail('features', f'{args.features} is not built for --classifier knn: its geometry is cosine similarity of the feature file')
+        if not 1 <= args.k <= vt._lib.KNN_MAX_K:
+            _fail('k', f'{args.k} is outside 1..{vt._lib.KNN_MAX_K}')
+        if not (args.temperature > 0 and np.isfinite(args.temperature)):
+            _fail('temperature', f'{args.temperature} is not a positive number')
+        args.normalize = True                                 # implied: the samples are drawn from the normalised volume
+
+    def configure(self, with_bg):
+        a, m = self.args, self.model
+        self.k, self.temperature, self.weights = ((a.k, a.temperature, a.knn_weights) if m is None
+                                                  else (m.k, m.temperature, m.weights))
+        self.with_bg = with_bg
+
+    def paths(self, d, num_samples, mode):
+        return knn_paths(d, knn_tag(num_samples, mode, self.k, self.temperature, self.weights, self.with_bg))
+
+    def check_features(self, f, name):
+        if f > 768:
+            _fail('classifier', f'knn takes F <= 768, {name} has F = {f}: reduce it first (reduce_features.py)')
+        if self.model is not None and self.model.n_features != f:
+            _fail('model', f'holds F = {self.model.n_features} features, {name} has F = {f}')
+
+    def fit(self, samples, targets, names):
+        return vt.knn.fit(samples, targets, k=self.k, temperature=self.temperature, weights=self.weights, class_names=names)
+
+    def predict(self, features, model, paths):
+        if not self.args.probs:
+            return vt.knn.predict(features, model)
+        idx, scores = vt.knn.predict(features, model, return_scores=True)
+        np.save(paths[3], vt.knn.probabilities(scores).cpu().numpy())
+        return idx
+
+    def describe(self, model):
+        return (f'{model.n_bank} bank samples ({np.bincount(model.bank_class, minlength=model.classes).tolist()} per class), '
+                f'k = {model.k}, {model.weights} weights' + (f', T = {model.temperature:g}' if model.weights == 'softmax' else ''))
+
+    def metrics(self, model):
+        return {'n_bank': model.n_bank, 'k': model.k, 'temperature': model.temperature, 'weights': model.weights}
+
+
 def main(argv=None):
     parser = ArgumentParser('Classify a feature volume with a support-vector machine or a random forest trained on annotated voxels')
     parser.add_argument('--data', type=str, required=True, help='directory holding volume, features and annotations / labels')
     parser.add_argument('--num-samples', type=float, default=0.0, help='annotations sampled per class from the labels (0: use the annotation file)')
     parser.add_argument('--sampling-mode', type=str, choices=['uniform', 'surface', 'both'], default='both', help='where samples are drawn from')
-    parser.add_argument('--classifier', type=str, choices=['svm', 'forest', 'mlp'], default=None, help='svm (the default), forest or mlp; --model FILE implies it')
+    parser.add_argument('--classifier', type=str, choices=['svm', 'forest', 'mlp', 'knn'], default=None, help='svm (the default), forest, mlp or knn; --model FILE implies it')
     parser.add_argument('--kernel', type=str, choices=list(vt.svm.KERNELS), default=None, help='svm: rbf (default) or linear')
     parser.add_argument('--C', type=float, default=None, help='svm: box constraint of the C-SVC (default 1.0)')
     parser.add_argument('--gamma', type=str, default=None, help="svm: RBF width: 'scale' (1 / (F var(samples)), default) or a number")
@@ -358,7 +438,10 @@ def main(argv=None):
     parser.add_argument('--batch', type=int, default=256, help='mlp: samples per step')
     parser.add_argument('--lr', type=float, default=1e-3, help='mlp: initial learning rate of the cosine schedule')
     parser.add_argument('--weight-decay', type=float, default=1e-2, help="mlp: AdamW's decoupled weight decay")
-    parser.add_argument('--probs', action='store_true', help='mlp: also write the per-class probabilities mlp_probs<tag>.npy')
+    parser.add_argument('--probs', action='store_true', help='mlp, knn: also write the per-class probabilities mlp_probs<tag>.npy / knn_probs<tag>.npy')
+    parser.add_argument('--k', type=int, default=20, help='knn: neighbours that vote (1..32)')
+    parser.add_argument('--temperature', type=float, default=0.07, metavar='T', help='knn: temperature of the weights exp(sim / T)')
+    parser.add_argument('--knn-weights', type=str, choices=list(vt.knn.WEIGHTS), default='softmax', help='knn: softmax (exp(sim / T), default) or uniform')
     parser.add_argument('--features', type=str, choices=list(FEATURE_TAGS), default='dino',
                         help='dino (default): the feature file; handcrafted: 11 channels computed from the volume itself; intensity: its intensity alone')
     parser.add_argument('--model', type=str, default=None, metavar='FILE', help='apply this saved model instead of fitting')
@@ -377,11 +460,12 @@ def main(argv=None):
     model = None
     kind = args.classifier
     if args.model:
-        of_file = 'mlp' if vt.mlp.is_mlp_file(args.model) else 'forest' if vt.forest.is_forest_file(args.model) else 'svm'
+        of_file = ('knn' if vt.knn.is_knn_file(args.model) else 'mlp' if vt.mlp.is_mlp_file(args.model)
+                   else 'forest' if vt.forest.is_forest_file(args.model) else 'svm')
         if kind is not None and kind != of_file:
             _fail('model', f'{args.model} does not hold a {kind} model')
         kind = of_file
-    clf = {'forest': _Forest, 'mlp': _Mlp}.get(kind, _Svm)(args)       # the classifier's own argument checks come first
+    clf = {'forest': _Forest, 'mlp': _Mlp, 'knn': _Knn}.get(kind, _Svm)(args)       # the classifier's own argument checks come first
     if args.model:
         try:
             model = clf.model = clf.module.load_model(args.model)

@@ -613,6 +613,34 @@ int vittf_mlp_decide(const uint16_t* feat, int32_t f, int64_t nvox, const float*
                      float* logits, uint8_t* probs, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weighted k-nearest-neighbour classification of a feature volume (vit-tf_amd/knn.py, classify_features.py --classifier
+ * knn): the k-NN of the DINO evaluation protocol.  There is no fit: the model is the bank of labelled samples itself.
+ * feat, nvox, voxel_norm: as for the SVM entries above (fp16 [f][nvox]; f a multiple of 32 in 32..768, padded inside with
+ * zero features to 32, 128, 384 or 768).  bank fp16 [n_bank][f], bank_class uint8 [n_bank] with values in 0..classes-1 (the
+ * caller checks them; the call trusts them), 1 <= n_bank <= VITTF_KNN_MAX_BANK, classes in 2..VITTF_KNN_MAX_CLASSES,
+ * 1 <= k <= min(VITTF_KNN_MAX_K, n_bank).
+ * Per voxel v: sim_s = bank_s . x_v (fp16 MFMAs, fp32 accumulation), times 1 / voxel_norm[v] in fp32 when voxel_norm is not
+ * NULL.  The neighbours are the k samples that come first under "larger sim first, then lower sample index", an IEEE
+ * comparison of exactly these fp32 values; rank 1 is the nearest.  Weights: w_j = 1 for inv_temperature = 0 (uniform);
+ * otherwise (inv_temperature = 1 / T > 0, finite) w_j = exp2((sim_j - sim_1) c) with c = fl32(log2(e) inv_temperature),
+ * formed on the host in double: w_1 = 1, nothing overflows.  scores[c][v] = the sum of w_j over the ranks j = 1..k whose
+ * sample has class c, added in fp32 in rank order; labels[v] = the arg-max of these fp32 scores, the lowest class among
+ * equal ones.  scores NULL or fp32 [classes][nvox]; nn_index (int32) and nn_sim (fp32) each NULL or [k][nvox], rank-major.
+ * Fixed order and no floating-point atomics: the same call gives the same bytes, and leaving any optional output NULL gives
+ * the same bytes in the others.  Two launches (bank images, decision); the volume is read once.
+ * ws: 16-byte aligned, >= vittf_knn_workspace_bytes(f, n_bank) = ceil(n_bank / 32) x (64 FP + 640) bytes (0 for a shape the
+ * call refuses); too small: VITTF_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------------- */
+#define VITTF_KNN_MAX_K 32        /* most neighbours: the sorted list of a lane lives in registers */
+#define VITTF_KNN_MAX_CLASSES 8   /* most classes of one bank */
+#define VITTF_KNN_MAX_BANK 65536  /* most samples of one bank: index and class share one 32-bit word */
+size_t vittf_knn_workspace_bytes(int32_t f, int32_t n_bank);
+int vittf_knn_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint16_t* bank, const uint8_t* bank_class,
+                     int32_t n_bank, int32_t classes, int32_t k, float inv_temperature, const float* voxel_norm,
+                     uint8_t* labels, float* scores, int32_t* nn_index, float* nn_sim, void* ws, size_t ws_bytes,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hand-crafted voxel features (vit-tf_amd/voxel_features.py, classify_features.py --features handcrafted | intensity): the
  * 11-channel per-voxel vector of the reference's classical baseline (predict_svm_rf.py:25-65) at the volume's own
  * resolution, as rows of the fp16 [f][nvox] matrix the two decision passes above take.

@@ -9,13 +9,20 @@ from .engine import HipViT                                          # noqa: F401
 from .extract import (sizing, feature_volume, pooled_axis, k_slices, DeviceVolume, AXIS_DIMS)     # noqa: F401
 from .similarity import sample_features3d, compute_similarities, assign_labels                    # noqa: F401
 from .synthetic import synthetic_volume, ct_like_volume, shapes                                   # noqa: F401
-from . import bilateral, components, forest, kmeans, mlp, pca, samplers, scores, similarity, svm, voxel_features, weights                    # noqa: F401
+from . import bilateral, components, forest, kmeans, knn, mlp, pca, samplers, scores, similarity, svm, voxel_features, weights                    # noqa: F401
 from .pca import (Basis, feature_gram, basis_from_gram, fit_basis, project, reduce_features,     # noqa: F401
                   save_basis, load_basis, rgb_volume)
 from .kmeans import Clustering, save_clustering, load_clustering                                 # noqa: F401
-from .svm import SvmModel, save_model, load_model                                                # noqa: F401
+from .svm import SvmModel, save_model                                                            # noqa: F401
 from .forest import ForestModel                                                                  # noqa: F401
 from .mlp import MlpModel                                                                        # noqa: F401
+from .knn import KnnModel                                                                        # noqa: F401
+
+
+def load_model(path):
+    """The model of a file svm.save_model or knn.save_model wrote: a k-NN bank names itself (format = 'vittf-knn-1'); anything
+    else goes to svm.load_model, as before."""
+    return knn.load_model(path) if knn.is_knn_file(path) else svm.load_model(path)
 
 __all__ = ['HipViT', 'feature_volume', 'compute_similarities', 'sample_features3d', 'assign_labels',
            'synthetic_state_dict', 'sizing', 'VittfError']

@@ -124,6 +124,8 @@ SIGNATURES = {
     'vittf_forest_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     'vittf_mlp_workspace_bytes': (_sz, [_i32, _P(_i32), _i32, _i32]),
     'vittf_mlp_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _P(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_knn_workspace_bytes': (_sz, [_i32, _i32]),
+    'vittf_knn_decide': (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'vittf_voxel_feature_stats_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'vittf_voxel_feature_stats': (C.c_int, [_vp, _i32, _i32, _i32, C.c_float, _vp, _vp, _sz, _vp]),
     'vittf_voxel_features': (C.c_int, [_vp, _i32, _i32, _i32, C.c_float, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp]),
@@ -187,7 +189,10 @@ FOREST_MAX_DEPTH = 64     # VITTF_FOREST_MAX_DEPTH: the deepest tree vittf_fores
 MLP_MAX_CLASSES = 8       # VITTF_MLP_MAX_CLASSES: classes of one vittf_mlp_decide head
 MLP_MAX_LAYERS = 2        # VITTF_MLP_MAX_LAYERS: hidden layers of one head
 MLP_MAX_WIDTH = 256       # VITTF_MLP_MAX_WIDTH: the widest hidden layer (a multiple of 32 from 32 up)
-VOXFEAT_CHANNELS = 11     # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
+KNN_MAX_K = 32            # VITTF_KNN_MAX_K: neighbours of one vittf_knn_decide call (the sorted list of a lane lives in registers)
+KNN_MAX_CLASSES = 8       # VITTF_KNN_MAX_CLASSES: classes of one bank
+KNN_MAX_BANK = 65536      # VITTF_KNN_MAX_BANK: samples of one bank
+VOXFEAT_CHANNELS = 11    # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
 KMEANS_SPANS = 128       # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
