@@ -724,6 +724,34 @@ int vittf_component_sizes(const int32_t* labels, int64_t nvox, int32_t* sizes, v
 int vittf_filter_components(const uint8_t* src, const int32_t* labels, const int32_t* sizes, int64_t nvox, int32_t min_size,
                             int32_t keep_label, int32_t fill, uint8_t* dst, void* stream);
 
+/* ---- exact Euclidean distance transform of a uint8 volume (vit-tf_amd/distance.py, score_labels.py) ----------------------
+ * A SITE is a voxel of the set that `value` selects -- 0..255: {src == value}; -1: {src != 0}, the select of
+ * vittf_label_components without its -2 -- with mode 0, or of its complement with mode 1 ({src != value}; {src == 0} for -1).
+ * d2_out (n0, n1, n2): for every voxel the squared Euclidean distance to the nearest site, 0 on a site
+ * (scipy.ndimage.distance_transform_edt(~sites) ** 2).  site_out, unless NULL: int32 (n0, n1, n2), the linear index
+ * (i0 * n1 + i1) * n2 + i2 of a site at that distance (the feature transform); among several nearest sites the one the fixed
+ * walk meets, not necessarily scipy's.  A volume without a site: VITTF_EDT_NO_SITE on every voxel (+inf in the fp32 output), -1
+ * in site_out, and the call returns VITTF_OK.  No atomics, every output is stored once: the same input gives the same bytes.
+ *
+ * vittf_edt_sq: unit spacing.  d2_out int32, exact (int32 arithmetic, at most 3 x 2047^2).
+ * vittf_edt_sq_weighted: d2 = sum_a w2_host[a] (x_a - s_a)^2, w2_host = the three squared voxel spacings (host doubles, finite
+ * and > 0).  fp64 arithmetic, rounded once to fp32: |d2_out - exact| <= 2^-24 exact + 2^-40 sum_a w2[a] (n_a - 1)^2.  With
+ * weights (1, 1, 1) it equals vittf_edt_sq converted to fp32.
+ *
+ * Every dimension in 1..VITTF_EDT_MAX_DIM and n0 n1 n2 < 2^31; value in -1..255; mode 0 or 1; src, d2_out, ws not NULL; d2_out
+ * and site_out 4-byte aligned, ws 8-byte aligned; anything else: VITTF_ERR_INVALID_ARG without a launch.  ws >=
+ * vittf_edt_workspace_bytes(n0, n1, n2) = 8 + 4 bytes per voxel, each part rounded up to 256 (0 for a shape the call refuses), the
+ * same for both entries; too small: VITTF_ERR_WORKSPACE.  src may sit at any byte alignment.
+ * Three launches: axis 2 by wave ballots and scans, then axis 1 and axis 0 as lower envelopes of parabolas (Meijster et al.
+ * 2000) on tiles of adjacent lines in LDS, as many lines as 80 KiB hold at n (4 or 8 + 4) bytes each. */
+#define VITTF_EDT_MAX_DIM 2048
+#define VITTF_EDT_NO_SITE 2147483647
+size_t vittf_edt_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int vittf_edt_sq(const uint8_t* src, int32_t n0, int32_t n1, int32_t n2, int32_t value, int32_t mode, int32_t* d2_out,
+                 int32_t* site_out, void* ws, size_t ws_bytes, void* stream);
+int vittf_edt_sq_weighted(const uint8_t* src, int32_t n0, int32_t n1, int32_t n2, int32_t value, int32_t mode,
+                          const double* w2_host, float* d2_out, int32_t* site_out, void* ws, size_t ws_bytes, void* stream);
+
 /* F.interpolate(mode='nearest') of a uint8 volume (n0, n1, n2) -> (o0, o1, o2): src index = min(floor(dst * (float)in /
  * out), in - 1) per dim.  equals < 0: plain resize -- the label up-sample of predict_ntf.py:217-218; equals = c in 0..255:
  * the resized class mask (src == c) as 0/1 -- evaluate_similarities.py:63 without materialising the full-size mask. */

@@ -139,6 +139,9 @@ SIGNATURES = {
     'vittf_label_components': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
     'vittf_component_sizes': (C.c_int, [_vp, _i64, _vp, _vp]),
     'vittf_filter_components': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    'vittf_edt_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'vittf_edt_sq': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'vittf_edt_sq_weighted': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _P(C.c_double), _vp, _vp, _vp, _sz, _vp]),
     'vittf_resize_nearest_u8': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     'vittf_widen_f16': (C.c_int, [_vp, _i64, _vp, _vp]),
     'vittf_bilateral_workspace_bytes': (_sz, [_i32, _i32, _i32, C.c_double, _i32]),
@@ -192,7 +195,9 @@ MLP_MAX_WIDTH = 256       # VITTF_MLP_MAX_WIDTH: the widest hidden layer (a mult
 KNN_MAX_K = 32            # VITTF_KNN_MAX_K: neighbours of one vittf_knn_decide call (the sorted list of a lane lives in registers)
 KNN_MAX_CLASSES = 8       # VITTF_KNN_MAX_CLASSES: classes of one bank
 KNN_MAX_BANK = 65536      # VITTF_KNN_MAX_BANK: samples of one bank
-VOXFEAT_CHANNELS = 11    # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
+EDT_MAX_DIM = 2048        # VITTF_EDT_MAX_DIM: the longest axis of a vittf_edt_sq volume (16-bit stack entries in LDS)
+EDT_NO_SITE = 2 ** 31 - 1  # VITTF_EDT_NO_SITE: the int32 squared distance of a volume without a site
+VOXFEAT_CHANNELS = 11   # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
 KMEANS_SPANS = 128       # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
