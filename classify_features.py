@@ -101,9 +101,15 @@ def svm_tag(num_samples, sampling_mode, kernel, normalize=False, background=True
     return f"{num_samples}{sampling_mode}{FEATURE_TAGS[features]}_{kernel}{'_norm' if normalize else ''}{'' if background else '_nobg'}"
 
 
-def output_paths(d, tag):
+def _paths(d, prefix, tag, extra=None):
+    """(prediction, model, metrics[, confidence volume]) files of a run in directory d."""
     d = Path(d)
-    return d / f'svm_pred{tag}.npy', d / f'svm_model{tag}.npz', d / f'svm_metrics{tag}.json'
+    paths = d / f'{prefix}_pred{tag}.npy', d / f'{prefix}_model{tag}.npz', d / f'{prefix}_metrics{tag}.json'
+    return paths if extra is None else paths + (d / f'{prefix}_{extra}{tag}.npy',)
+
+
+def output_paths(d, tag):
+    return _paths(d, 'svm', tag)
 
 
 def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='sqrt', background=True, features='dino'):
@@ -113,8 +119,7 @@ def forest_tag(num_samples, sampling_mode, trees, max_depth=None, max_features='
 
 
 def forest_paths(d, tag):
-    d = Path(d)
-    return d / f'rf_pred{tag}.npy', d / f'rf_model{tag}.npz', d / f'rf_metrics{tag}.json', d / f'rf_votes{tag}.npy'
+    return _paths(d, 'rf', tag, 'votes')
 
 
 def mlp_tag(num_samples, sampling_mode, hidden=(), normalize=False, background=True, features='dino'):
@@ -124,8 +129,7 @@ def mlp_tag(num_samples, sampling_mode, hidden=(), normalize=False, background=T
 
 
 def mlp_paths(d, tag):
-    d = Path(d)
-    return d / f'mlp_pred{tag}.npy', d / f'mlp_model{tag}.npz', d / f'mlp_metrics{tag}.json', d / f'mlp_probs{tag}.npy'
+    return _paths(d, 'mlp', tag, 'probs')
 
 
 def knn_tag(num_samples, sampling_mode, k=20, temperature=0.07, weights='softmax', background=True):
@@ -135,8 +139,7 @@ def knn_tag(num_samples, sampling_mode, k=20, temperature=0.07, weights='softmax
 
 
 def knn_paths(d, tag):
-    d = Path(d)
-    return d / f'knn_pred{tag}.npy', d / f'knn_model{tag}.npz', d / f'knn_metrics{tag}.json', d / f'knn_probs{tag}.npy'
+    return _paths(d, 'knn', tag, 'probs')
 
 
 def find_feature_file(d):
@@ -159,15 +162,63 @@ def _draw(mode, lab, n, class_id=None):
 SVM_DEFAULTS = {'kernel': 'rbf', 'C': 1.0, 'gamma': 'scale', 'tol': 1e-3}
 
 
-class _Svm:
-    """The support-vector side of main: its argument checks, file names, fit, pass over the volume and report."""
-    name, module = 'SVM', vt.svm
+class _Classifier:
+    """What the four sides of main share.  A side has its argument checks (__init__), file names (paths), fit and report
+    (describe, metrics); `kind` is its --classifier value, `extra_flag` the flag that asks for its confidence volume (the fourth
+    of its paths), `confidence` what turns the extra output of its predict into that volume's uint8."""
+    kind = extra_flag = None
 
     def __init__(self, args):
+        self.args, self.model = args, None
+
+    def refuse_svm_flags(self):
+        for k in SVM_DEFAULTS:
+            if getattr(self.args, k) is not None:
+                _fail(k, f'does not apply to --classifier {self.kind}')
+
+    def configure(self, with_bg):
+        """Called once the background decision is known (a loaded model brings its own): fixes the tag's ingredients."""
+        self.with_bg = with_bg
+
+    def check_features(self, f, name, holds='fitted on'):
+        if self.model is not None and self.model.n_features != f:
+            _fail('model', f'{holds} F = {self.model.n_features} features, {name} has F = {f}')
+
+    def wants_extra(self):
+        return self.extra_flag is not None and getattr(self.args, self.extra_flag)
+
+    def confidence(self, model, extra):
+        return extra
+
+    def predict(self, features, model, paths):
+        if not self.wants_extra():
+            return self.module.predict(features, model)
+        idx, extra = self.module.predict(features, model, True)
+        np.save(paths[3], self.confidence(model, extra).cpu().numpy())
+        return idx
+
+    def predict_volume(self, volume, stats, channels, model, paths):
+        if not self.wants_extra():
+            return vt.voxel_features.classify(volume, model, channels, stats)
+        idx = torch.empty(volume.numel(), dtype=torch.uint8, device=volume.device)
+        # slab by slab: the uint32 votes of a whole volume (C x 537 MB at 512^3) never exist, only their uint8 shares
+        conf = np.empty((model.classes, volume.numel()), np.uint8)
+        for start, n, labels, extra in vt.voxel_features.slabs(volume, model, channels, stats, want_votes=True):
+            idx[start:start + n] = labels
+            conf[:, start:start + n] = self.confidence(model, extra).cpu().numpy()
+        np.save(paths[3], conf.reshape((model.classes,) + tuple(volume.shape)))
+        return idx.reshape(tuple(volume.shape))
+
+
+class _Svm(_Classifier):
+    """The support-vector side of main: its argument checks, file names, fit, pass over the volume and report."""
+    name, module, kind = 'SVM', vt.svm, 'svm'
+
+    def __init__(self, args):
+        super().__init__(args)
         for k, v in SVM_DEFAULTS.items():
             if getattr(args, k) is None:
                 setattr(args, k, v)
-        self.args, self.model = args, None
         if not (args.C > 0 and np.isfinite(args.C)):
             _fail('C', f'{args.C} is not a positive number')
         if not (args.tol > 0 and np.isfinite(args.tol)):
@@ -182,10 +233,9 @@ class _Svm:
                 _fail('gamma', f'{args.gamma} is negative or not finite')
 
     def configure(self, with_bg):
-        """Called once the background decision is known (a loaded model brings its own): fixes the tag's ingredients."""
+        super().configure(with_bg)
         m = self.model
         self.kernel, self.normalize = (self.args.kernel, self.args.normalize) if m is None else (m.kernel, m.normalize)
-        self.with_bg = with_bg
 
     def paths(self, d, num_samples, mode):
         return output_paths(d, svm_tag(num_samples, mode, self.kernel, self.normalize, self.with_bg, self.args.features))
@@ -193,19 +243,12 @@ class _Svm:
     def check_features(self, f, name):
         if self.kernel == 'rbf' and f > 768:
             _fail('kernel', f'the RBF kernel takes F <= 768, {name} has F = {f}: reduce it first (reduce_features.py)')
-        if self.model is not None and self.model.sv.shape[1] != f:
-            _fail('model', f'fitted on F = {self.model.sv.shape[1]} features, {name} has F = {f}')
+        super().check_features(f, name)
 
     def fit(self, samples, targets, names):
         a = self.args
         return vt.svm.fit(samples, targets, kernel=self.kernel, C=a.C, gamma=self.gamma, tol=a.tol, normalize=self.normalize,
                           class_names=names)
-
-    def predict(self, features, model, paths):
-        return vt.svm.predict(features, model)
-
-    def predict_volume(self, volume, stats, channels, model, paths):
-        return vt.voxel_features.classify(volume, model, channels, stats)
 
     def describe(self, model):
         return f'{model.sv.shape[0]} support vectors ({model.n_support.tolist()} per class)'
@@ -214,15 +257,13 @@ class _Svm:
         return {'n_sv': int(model.sv.shape[0])}
 
 
-class _Forest:
+class _Forest(_Classifier):
     """The random-forest side of main."""
-    name, module = 'RF', vt.forest
+    name, module, kind, extra_flag = 'RF', vt.forest, 'forest', 'votes'
 
     def __init__(self, args):
-        self.args, self.model = args, None
-        for k in SVM_DEFAULTS:
-            if getattr(args, k) is not None:
-                _fail(k, 'does not apply to --classifier forest')
+        super().__init__(args)
+        self.refuse_svm_flags()
         if args.normalize:
             _fail('normalize', 'is not built for --classifier forest')
         if not 1 <= args.trees <= vt._lib.FOREST_MAX_TREES:
@@ -245,9 +286,6 @@ class _Forest:
         self.max_features = mf
         print('Note: --kernel, --C, --gamma and --tol do not apply to --classifier forest')
 
-    def configure(self, with_bg):
-        self.with_bg = with_bg
-
     def paths(self, d, num_samples, mode):
         a, m = self.args, self.model
         if m is not None:                                     # a loaded forest: what the file can tell
@@ -257,8 +295,7 @@ class _Forest:
         return forest_paths(d, tag)
 
     def check_features(self, f, name):
-        if self.model is not None and self.model.n_features != f:
-            _fail('model', f'fitted on F = {self.model.n_features} features, {name} has F = {f}')
+        super().check_features(f, name)
         if self.model is None and isinstance(self.max_features, int) and self.max_features > f:
             _fail('max-features', f'{self.max_features} is more than the F = {f} of {name}')
 
@@ -267,26 +304,9 @@ class _Forest:
         return vt.forest.fit(samples, targets, trees=a.trees, max_features=self.max_features, max_depth=a.max_depth,
                              min_samples_leaf=a.min_samples_leaf, bootstrap=not a.no_bootstrap, seed=a.seed, class_names=names)
 
-    def predict(self, features, model, paths):
-        if not self.args.votes:
-            return vt.forest.predict(features, model)
-        idx, votes = vt.forest.predict(features, model, return_votes=True)
+    def confidence(self, model, votes):
         wide = votes.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-        np.save(paths[3], (wide * 255 // (model.trees * 65535)).to(torch.uint8).cpu().numpy())
-        return idx
-
-    def predict_volume(self, volume, stats, channels, model, paths):
-        if not self.args.votes:
-            return vt.voxel_features.classify(volume, model, channels, stats)
-        idx = torch.empty(volume.numel(), dtype=torch.uint8, device=volume.device)
-        # slab by slab: the uint32 votes of a whole volume (C x 537 MB at 512^3) never exist, only their uint8 shares
-        conf = np.empty((model.classes, volume.numel()), np.uint8)
-        for start, n, labels, votes in vt.voxel_features.slabs(volume, model, channels, stats, want_votes=True):
-            idx[start:start + n] = labels
-            wide = votes.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-            conf[:, start:start + n] = (wide * 255 // (model.trees * 65535)).to(torch.uint8).cpu().numpy()
-        np.save(paths[3], conf.reshape((model.classes,) + tuple(volume.shape)))
-        return idx.reshape(tuple(volume.shape))
+        return (wide * 255 // (model.trees * 65535)).to(torch.uint8)
 
     def describe(self, model):
         return f'{model.trees} trees, {model.n_nodes} nodes, depth {model.max_depth}'
@@ -295,15 +315,13 @@ class _Forest:
         return {'n_trees': model.trees, 'n_nodes': model.n_nodes, 'max_depth': model.max_depth}
 
 
-class _Mlp:
-    """The MLP-head side of main."""
-    name, module = 'MLP', vt.mlp
+class _Mlp(_Classifier):
+    """The MLP-head side of main (its uint8 probabilities are the confidence volume as they are)."""
+    name, module, kind, extra_flag = 'MLP', vt.mlp, 'mlp', 'probs'
 
     def __init__(self, args):
-        self.args, self.model = args, None
-        for k in SVM_DEFAULTS:
-            if getattr(args, k) is not None:
-                _fail(k, 'does not apply to --classifier mlp')
+        super().__init__(args)
+        self.refuse_svm_flags()
         try:
             self.hidden = vt.mlp.parse_hidden(args.hidden)
         except ValueError:
@@ -321,39 +339,17 @@ class _Mlp:
             _fail('weight-decay', f'{args.weight_decay} is negative or not finite')
 
     def configure(self, with_bg):
+        super().configure(with_bg)
         m = self.model
         self.hidden, self.normalize = (self.hidden, self.args.normalize) if m is None else (m.hidden, m.normalize)
-        self.with_bg = with_bg
 
     def paths(self, d, num_samples, mode):
         return mlp_paths(d, mlp_tag(num_samples, mode, self.hidden, self.normalize, self.with_bg, self.args.features))
-
-    def check_features(self, f, name):
-        if self.model is not None and self.model.n_features != f:
-            _fail('model', f'fitted on F = {self.model.n_features} features, {name} has F = {f}')
 
     def fit(self, samples, targets, names):
         a = self.args
         return vt.mlp.fit(samples, targets, hidden=self.hidden, epochs=a.epochs, batch=a.batch, lr=a.lr, weight_decay=a.weight_decay,
                           seed=a.seed, normalize=self.normalize, class_names=names)
-
-    def predict(self, features, model, paths):
-        if not self.args.probs:
-            return vt.mlp.predict(features, model)
-        idx, probs = vt.mlp.predict(features, model, return_probs=True)
-        np.save(paths[3], probs.cpu().numpy())
-        return idx
-
-    def predict_volume(self, volume, stats, channels, model, paths):
-        if not self.args.probs:
-            return vt.voxel_features.classify(volume, model, channels, stats)
-        idx = torch.empty(volume.numel(), dtype=torch.uint8, device=volume.device)
-        conf = np.empty((model.classes, volume.numel()), np.uint8)               # slab by slab, as the forest's votes
-        for start, n, labels, probs in vt.voxel_features.slabs(volume, model, channels, stats, want_votes=True):
-            idx[start:start + n] = labels
-            conf[:, start:start + n] = probs.cpu().numpy()
-        np.save(paths[3], conf.reshape((model.classes,) + tuple(volume.shape)))
-        return idx.reshape(tuple(volume.shape))
 
     def describe(self, model):
         return f'hidden {list(model.hidden)}, {model.n_params} parameters, training accuracy {model.train_accuracy:.4f}'
@@ -363,15 +359,13 @@ class _Mlp:
                 'train_accuracy': model.train_accuracy}
 
 
-class _Knn:
+class _Knn(_Classifier):
     """The k-nearest-neighbour side of main."""
-    name, module = 'KNN', vt.knn
+    name, module, kind, extra_flag = 'KNN', vt.knn, 'knn', 'probs'
 
     def __init__(self, args):
-        self.args, self.model = args, None
-        for k in SVM_DEFAULTS:
-            if getattr(args, k) is not None:
-                _fail(k, 'does not apply to --classifier knn')
+        super().__init__(args)
+        self.refuse_svm_flags()
         if args.votes:
             _fail('votes', 'does not apply to --classifier knn (--probs writes its per-class shares)')
         if args.features != 'dino':
@@ -383,10 +377,10 @@ class _Knn:
         args.normalize = True                                 # implied: the samples are drawn from the normalised volume
 
     def configure(self, with_bg):
+        super().configure(with_bg)
         a, m = self.args, self.model
         self.k, self.temperature, self.weights = ((a.k, a.temperature, a.knn_weights) if m is None
                                                   else (m.k, m.temperature, m.weights))
-        self.with_bg = with_bg
 
     def paths(self, d, num_samples, mode):
         return knn_paths(d, knn_tag(num_samples, mode, self.k, self.temperature, self.weights, self.with_bg))
@@ -394,18 +388,13 @@ class _Knn:
     def check_features(self, f, name):
         if f > 768:
             _fail('classifier', f'knn takes F <= 768, {name} has F = {f}: reduce it first (reduce_features.py)')
-        if self.model is not None and self.model.n_features != f:
-            _fail('model', f'holds F = {self.model.n_features} features, {name} has F = {f}')
+        super().check_features(f, name, 'holds')
 
     def fit(self, samples, targets, names):
         return vt.knn.fit(samples, targets, k=self.k, temperature=self.temperature, weights=self.weights, class_names=names)
 
-    def predict(self, features, model, paths):
-        if not self.args.probs:
-            return vt.knn.predict(features, model)
-        idx, scores = vt.knn.predict(features, model, return_scores=True)
-        np.save(paths[3], vt.knn.probabilities(scores).cpu().numpy())
-        return idx
+    def confidence(self, model, scores):
+        return vt.knn.probabilities(scores)
 
     def describe(self, model):
         return (f'{model.n_bank} bank samples ({np.bincount(model.bank_class, minlength=model.classes).tolist()} per class), '
@@ -460,8 +449,7 @@ def main(argv=None):
     model = None
     kind = args.classifier
     if args.model:
-        of_file = ('knn' if vt.knn.is_knn_file(args.model) else 'mlp' if vt.mlp.is_mlp_file(args.model)
-                   else 'forest' if vt.forest.is_forest_file(args.model) else 'svm')
+        of_file = {vt.knn.FORMAT: 'knn', vt.mlp.FORMAT: 'mlp', vt.forest.FORMAT: 'forest'}.get(vt._classify.file_format(args.model), 'svm')
         if kind is not None and kind != of_file:
             _fail('model', f'{args.model} does not hold a {kind} model')
         kind = of_file
@@ -472,10 +460,9 @@ def main(argv=None):
         except (OSError, ValueError, KeyError) as e:
             _fail('model', e)
     if own and model is not None:
-        f_model = model.sv.shape[1] if kind in (None, 'svm') else model.n_features
-        if f_model != 32:
-            _fail('model', f'fitted on F = {f_model} features, --features {args.features} gives F = 32 (its rows in a zeroed 32-row matrix)')
-        if kind != 'forest' and model.normalize:
+        if model.n_features != 32:
+            _fail('model', f'fitted on F = {model.n_features} features, --features {args.features} gives F = 32 (its rows in a zeroed 32-row matrix)')
+        if model.normalize:
             _fail('model', f'fitted with --normalize, which --features {args.features} refuses')
     has_labels = (d / 'labels.npy').exists()
     background = args.background

@@ -202,16 +202,19 @@ def _model(kind, channels=11):
     names = ['background', 'ntf1', 'ntf2']
     if kind == 'forest':
         return vt.forest.fit(samples, values, trees=8, bootstrap=False, seed=1, class_names=names)
+    if kind == 'mlp':
+        return vt.mlp.fit(samples, values, hidden=(32,), epochs=60, batch=40, lr=1e-2, seed=1, class_names=names)
     return vt.svm.fit(samples, values, kernel=kind, class_names=names)
 
 
-@pytest.mark.parametrize('kind', ['forest', 'rbf', 'linear'])
+@pytest.mark.parametrize('kind', ['forest', 'rbf', 'linear', 'mlp'])
 def test_classify_streams_the_dense_decision(gpu, kind):
     vol, lab, st, ann = _boxes()
     model = _model(kind)
     nvox = vol.numel()
     x = vf.compose(vol, st)
-    decide = vt.forest.decide if kind == 'forest' else (lambda x, m, v: vt.svm.decide(x, m, None, v))
+    decide = {'forest': vt.forest.decide, 'mlp': lambda x, m, v: vt.mlp.decide(x, m, None, False, v)[::2]}.get(
+        kind, lambda x, m, v: vt.svm.decide(x, m, None, v))   # votes, probabilities (of a (32,) head) or decisions
     want, want_votes = decide(x, model, True)
     want, want_votes = want.cpu().numpy(), want_votes.cpu().numpy()
     for slab in (4104, 5000, 1 << 24):                        # 4 slabs (last: 1128 voxels), 3 slabs (last: 3440), one

@@ -5,7 +5,13 @@
   python tools/lib_ab.py tools/micro/build/libvittf_prev.so attention [result.json] [slices]
       the attention family and the producers of its operands: outputs AND workspaces compared byte for byte over the token
       counts where the kernels change path, then each library timed twice in turn (other, tree, other, tree) on the ViT-S /
-      ViT-B shapes; exit status 1 when any comparison differs"""
+      ViT-B shapes; exit status 1 when any comparison differs
+  python tools/lib_ab.py tools/micro/build/libvittf_prev.so classifiers [result.json]
+      the decision entries of the classifiers (RBF and linear SVM, k-NN, MLP head) and the two other users of feat_rows.h's
+      score loop (PCA projection, k-means assignment): outputs AND workspaces compared byte for byte over the smallest shapes
+      that reach every template and edge of the bank frame (csrc/bank_frame.h), then each library timed twice in turn on the
+      shapes of tools/svm_step.py, knn_step.py and mlp_step.py (64^3 x 384, 1024 rows); exit status 1 when any comparison
+      differs"""
 import ctypes as C
 import json
 import os
@@ -32,6 +38,66 @@ def same_bytes(a, b):
     return torch.equal(a.view(torch.uint8), b.view(torch.uint8))
 
 
+def both_same(libs, run):
+    """run(lib) -> [tensors]: True when both libraries leave the same bytes in every one of them."""
+    outs = []
+    for k in ('other', 'tree'):
+        outs.append(run(libs[k]))
+        torch.cuda.synchronize()
+    return all(same_bytes(a, b) for a, b in zip(*outs))
+
+
+def timed(libs, call, rounds=7, reps=10):
+    """{'other': [median, median], 'tree': [median, median]} in ms per call(lib): other, tree, other, tree, each figure the
+    median of `rounds` event pairs around `reps` calls -- more of them where a call is short, so that a pair spans 5 ms."""
+    med = {'other': [], 'tree': []}
+    for k in ('other', 'tree'):                               # warm both up: clocks, code objects, caches
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            call(libs[k])
+        b.record()
+        torch.cuda.synchronize()
+    reps = max(reps, min(500, int(5.0 * reps / max(a.elapsed_time(b), 1e-3))))
+    for _ in range(2):
+        for k in ('other', 'tree'):
+            call(libs[k])
+            ts = []
+            for _ in range(rounds):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(reps):
+                    call(libs[k])
+                b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) / reps)
+            med[k].append(round(statistics.median(ts), 4))
+    return med
+
+
+def report(bits, times, out_json, count_by=None):
+    """Prints both tables, writes them to out_json and returns the exit status: 1 when a byte comparison differs.  The json
+    lists the cases by name, or, with count_by(case) -> group, how many ran in each group (the loops define them)."""
+    for k, same in bits.items():
+        print(f'{"identical" if same else "DIFFERENT":9s}  {k}', flush=True)
+    different = [k for k, same in bits.items() if not same]
+    print(f'byte comparisons: {len(bits) - len(different)} identical, {len(different)} different', flush=True)
+    cases = sorted(bits) if count_by is None else {g: sum(count_by(k) == g for k in bits) for g in sorted(set(map(count_by, bits)))}
+    result = {'byte_comparisons': {'identical': len(bits) - len(different), 'different': different, 'cases': cases},
+              'ms_per_call': times}
+    for k, v in times.items():
+        # the tree's slower median against the other's slower median plus the spread of the other's own two rounds
+        v['other_spread'] = round(abs(v['other'][0] - v['other'][1]), 4)
+        v['within_spread'] = round(max(v['tree']) - max(v['other']), 4) <= v['other_spread']       # (figures of 4 decimals)
+        print(f'{k}: other {v["other"]}  tree {v["tree"]} ms, spread of other {v["other_spread"]}: '
+              f'{"within" if v["within_spread"] else "BEYOND"}', flush=True)
+    if out_json:
+        os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
+        with open(out_json, 'w') as f:
+            json.dump(result, f, indent=1)
+    return 1 if different else 0
+
+
 def attention_bits(libs, dev):
     """-> {case: identical} -- every case runs both libraries on the same inputs, outputs and workspaces pre-filled alike."""
     from vit_tf_amd import weights
@@ -46,12 +112,7 @@ def attention_bits(libs, dev):
             x[:, :heads * 64] *= qscale
         return x.to(dt).to(dev)
 
-    def both(run):
-        outs = []
-        for k in ('other', 'tree'):
-            outs.append(run(libs[k]))
-            torch.cuda.synchronize()
-        return all(same_bytes(a, b) for a, b in zip(*outs))
+    both = lambda run: both_same(libs, run)                   # noqa: E731
 
     def attention(qkv, batch, tokens, heads, dtn, pre):
         def run(lib):
@@ -131,32 +192,12 @@ def attention_bits(libs, dev):
     return res
 
 
-def attention_times(libs, dev, slices, rounds=7, reps=10):
-    """-> {shape: {'other': [median, median], 'tree': [median, median]}} in ms per call: other, tree, other, tree."""
+def attention_times(libs, dev, slices):
+    """-> {shape: timed(..)}."""
     tokens = 4097
     st = _lib.stream_ptr
     qscale = 0.125 * 1.4426950408889634
     times = {}
-
-    def timed(call):
-        med = {'other': [], 'tree': []}
-        for _ in range(3):
-            call(libs['tree'])
-        torch.cuda.synchronize()
-        for _ in range(2):
-            for k in ('other', 'tree'):
-                call(libs[k])
-                ts = []
-                for _ in range(rounds):
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    for _ in range(reps):
-                        call(libs[k])
-                    b.record()
-                    torch.cuda.synchronize()
-                    ts.append(a.elapsed_time(b) / reps)
-                med[k].append(round(statistics.median(ts), 4))
-        return med
 
     for name, heads, pre in (('attention q_prescaled=1 ViT-S (6 heads)', 6, 1), ('attention q_prescaled=1 ViT-B (12 heads)', 12, 1),
                              ('attention q_prescaled=0 ViT-S (6 heads)', 6, 0)):
@@ -165,7 +206,7 @@ def attention_times(libs, dev, slices, rounds=7, reps=10):
         if pre:
             qkv[:, :heads * 64] *= qscale
         out = torch.empty(slices * tokens, heads * 64, dtype=torch.half, device=dev)
-        times[f'{name} {slices}x{tokens} fp16'] = timed(lambda lib: _lib.check(lib.vittf_attention(
+        times[f'{name} {slices}x{tokens} fp16'] = timed(libs, lambda lib: _lib.check(lib.vittf_attention(
             _lib.ptr(qkv), _lib.ptr(out), slices, tokens, heads, _lib.FP16, pre, st())))
         del qkv, out
     # attention on fp8 rows at ViT-B: the projection (the tree's) fills q8 / k8 and their scales once
@@ -182,7 +223,7 @@ def attention_times(libs, dev, slices, rounds=7, reps=10):
     _lib.check(libs['tree'].vittf_gemm_qkv_fp8(_lib.ptr(a), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(qkv), rows, n, kk, tokens, heads, _lib.FP16,
                                                _lib.ptr(ws), nws, st()))
     del a
-    times[f'attention_fp8_rows ViT-B (12 heads) {slices}x{tokens} fp16'] = timed(lambda lib: _lib.check(lib.vittf_attention_fp8_rows(
+    times[f'attention_fp8_rows ViT-B (12 heads) {slices}x{tokens} fp16'] = timed(libs, lambda lib: _lib.check(lib.vittf_attention_fp8_rows(
         _lib.ptr(qkv), _lib.ptr(out), slices, tokens, heads, _lib.FP16, _lib.ptr(ws), nws, st())))
     return times
 
@@ -191,26 +232,195 @@ def attention_mode(other, out_json, slices):
     libs = load_both(other, ('vittf_attention', 'vittf_attention_fp8', 'vittf_attention_fp8_rows', 'vittf_attention_fp8_workspace_bytes',
                              'vittf_gemm_qkv_fp8', 'vittf_gemm', 'vittf_gemm_as'))
     dev = torch.device('cuda', 0)
-    bits = attention_bits(libs, dev)
-    for k, same in bits.items():
-        print(f'{"identical" if same else "DIFFERENT":9s}  {k}', flush=True)
-    different = [k for k, same in bits.items() if not same]
-    print(f'byte comparisons: {len(bits) - len(different)} identical, {len(different)} different', flush=True)
-    result = {'byte_comparisons': {'identical': len(bits) - len(different), 'different': different, 'cases': sorted(bits)}}
-    result['ms_per_call'] = attention_times(libs, dev, slices)
-    for k, v in result['ms_per_call'].items():
-        print(f'{k}: other {v["other"]}  tree {v["tree"]} ms', flush=True)
-    if out_json:
-        os.makedirs(os.path.dirname(os.path.abspath(out_json)), exist_ok=True)
-        with open(out_json, 'w') as f:
-            json.dump(result, f, indent=1)
-    return 1 if different else 0
+    return report(attention_bits(libs, dev), attention_times(libs, dev, slices), out_json)
+
+
+# ------------------------------------------------------------------------------------------------ classifiers
+CLASSIFIER_ENTRIES = ('vittf_svm_rbf_decide', 'vittf_svm_rbf_workspace_bytes', 'vittf_svm_linear_decide', 'vittf_knn_decide',
+                      'vittf_knn_workspace_bytes', 'vittf_mlp_decide', 'vittf_mlp_workspace_bytes', 'vittf_feature_project',
+                      'vittf_kmeans_assign')
+
+
+class Calls:
+    """The raw decision calls on one device; each method returns run(lib) -> [what the call wrote].  Every output and
+    workspace is a new tensor pre-filled the same way before the call (fresh), or, for the timings, one tensor reused."""
+
+    def __init__(self, libs, dev, fresh=True):
+        self.libs, self.dev, self.fresh, self.kept = libs, dev, fresh, {}
+
+    def volume(self, f, nvox, seed):
+        g = torch.Generator().manual_seed(seed)
+        x = (torch.randn(f, nvox, generator=g) + torch.randn(f, 1, generator=g)).half().to(self.dev)
+        return x, x.float().norm(dim=0).clamp_min(1e-6).contiguous()
+
+    def rows(self, s, f, seed, unit=False):
+        r = torch.randn(s, f, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+        return (torch.nn.functional.normalize(r, dim=1) if unit else r).half().to(self.dev)
+
+    def out(self, shape, dtype, fill=7):
+        if not self.fresh and (shape, dtype) in self.kept:
+            return self.kept[shape, dtype]
+        t = self.kept[shape, dtype] = torch.full(shape, fill, dtype=dtype, device=self.dev)
+        return t
+
+    def workspace(self, name, *args):
+        n = getattr(self.libs['tree'], name)(*args)
+        assert n and n == getattr(self.libs['other'], name)(*args), (name, args, n)
+        return n
+
+    def rbf(self, x, norm, sv, classes, seed):
+        f, nvox = x.shape
+        s, pairs = sv.shape[0], classes * (classes - 1) // 2
+        g = torch.Generator().manual_seed(seed)
+        coef = torch.randn(pairs, s, generator=g).to(self.dev)
+        b = (0.1 * torch.randn(pairs, generator=g)).to(self.dev)
+        nws = self.workspace('vittf_svm_rbf_workspace_bytes', f, s, classes)
+
+        def run(lib):
+            ws, labels, dec = self.out((nws,), torch.uint8, 0xff), self.out((nvox,), torch.uint8), self.out((pairs, nvox), torch.float32)
+            _lib.check(lib.vittf_svm_rbf_decide(_lib.ptr(x), f, nvox, _lib.ptr(sv), _lib.ptr(coef), _lib.ptr(b), s, classes, 1.0 / f,
+                                                _lib.ptr(norm), _lib.ptr(labels), _lib.ptr(dec), _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [labels, dec, ws]
+        return run
+
+    def linear(self, x, norm, classes, seed):
+        f, nvox = x.shape
+        pairs = classes * (classes - 1) // 2
+        g = torch.Generator().manual_seed(seed)
+        w = (torch.randn(pairs, f, generator=g) / f ** 0.5).to(self.dev)
+        b = (0.1 * torch.randn(pairs, generator=g)).to(self.dev)
+
+        def run(lib):
+            labels, dec = self.out((nvox,), torch.uint8), self.out((pairs, nvox), torch.float32)
+            _lib.check(lib.vittf_svm_linear_decide(_lib.ptr(x), f, nvox, _lib.ptr(w), _lib.ptr(b), classes, _lib.ptr(norm), _lib.ptr(labels),
+                                                   _lib.ptr(dec), _lib.stream_ptr()))
+            return [labels, dec]
+        return run
+
+    def knn(self, x, norm, bank, classes, k, inv_t, seed, outputs=True):
+        f, nvox = x.shape
+        s = bank.shape[0]
+        cls = torch.sort(torch.randint(0, classes, (s,), generator=torch.Generator().manual_seed(seed))).values.to(torch.uint8).to(self.dev)
+        nws = self.workspace('vittf_knn_workspace_bytes', f, s)
+
+        def run(lib):
+            ws, labels = self.out((nws,), torch.uint8, 0xff), self.out((nvox,), torch.uint8)
+            extra = [self.out((classes, nvox), torch.float32), self.out((k, nvox), torch.int32), self.out((k, nvox), torch.float32)] if outputs else [None] * 3
+            _lib.check(lib.vittf_knn_decide(_lib.ptr(x), f, nvox, _lib.ptr(bank), _lib.ptr(cls), s, classes, k, inv_t, _lib.ptr(norm),
+                                            _lib.ptr(labels), *[_lib.ptr(e) for e in extra], _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [labels, ws] + [e for e in extra if e is not None]
+        return run
+
+    def mlp(self, x, hidden, classes, seed):
+        f, nvox = x.shape
+        dims = (f,) + tuple(hidden) + (classes,)
+        g = torch.Generator().manual_seed(seed)
+        w = torch.cat([(torch.randn(dims[i + 1], dims[i], generator=g) / dims[i] ** 0.5).reshape(-1) for i in range(len(dims) - 1)]).to(self.dev)
+        b = torch.cat([0.1 * torch.randn(dims[i + 1], generator=g) for i in range(len(dims) - 1)]).to(self.dev)
+        widths = (C.c_int32 * max(len(hidden), 1))(*hidden)
+        nws = self.workspace('vittf_mlp_workspace_bytes', f, widths, len(hidden), classes)
+
+        def run(lib):
+            ws, labels = self.out((nws,), torch.uint8, 0xff), self.out((nvox,), torch.uint8)
+            logits, probs = self.out((classes, nvox), torch.float32), self.out((classes, nvox), torch.uint8)
+            _lib.check(lib.vittf_mlp_decide(_lib.ptr(x), f, nvox, _lib.ptr(w), _lib.ptr(b), widths, len(hidden), classes, None, _lib.ptr(labels),
+                                            _lib.ptr(logits), _lib.ptr(probs), _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [labels, logits, probs]
+        return run
+
+    def project(self, x, k, seed):
+        f, nvox = x.shape
+        g = torch.Generator().manual_seed(seed)
+        comp, off = (torch.randn(k, f, generator=g) / f ** 0.5).to(self.dev), torch.randn(f, generator=g).to(self.dev)
+
+        def run(lib):
+            out = self.out((k, nvox), torch.float16)
+            _lib.check(lib.vittf_feature_project(_lib.ptr(x), f, nvox, _lib.ptr(comp), _lib.ptr(off), k, _lib.ptr(out), _lib.stream_ptr()))
+            return [out]
+        return run
+
+    def assign(self, x, c, seed):
+        f, nvox = x.shape
+        cent = torch.randn(c, f, generator=torch.Generator().manual_seed(seed))
+        half = (0.5 * cent.double().pow(2).sum(1)).float().to(self.dev)
+        cent = cent.to(self.dev)
+
+        def run(lib):
+            labels, best = self.out((nvox,), torch.uint8), self.out((nvox,), torch.float32)
+            _lib.check(lib.vittf_kmeans_assign(_lib.ptr(x), f, nvox, _lib.ptr(cent), _lib.ptr(half), c, _lib.ptr(labels), _lib.ptr(best),
+                                               _lib.stream_ptr()))
+            return [labels, best]
+        return run
+
+
+def classifier_bits(libs, dev):
+    """-> {case: identical}: the smallest shapes that reach every template and edge of the frame."""
+    calls, res = Calls(libs, dev), {}
+    same = lambda run: both_same(libs, run)                   # noqa: E731
+    inv_t = float(torch.tensor(1.0 / 0.07, dtype=torch.float32))
+    for f in (32, 64, 384, 768):                               # F = 64 pads to FP = 128
+        for nvox in (1, 127, 128, 129, 1024):                  # 129: unaligned rows and a second workgroup
+            x, norm = calls.volume(f, nvox, f + nvox)
+            for s in (1, 31, 32, 33, 65):                      # rows of the bank: chunk edges; 65 at F = 384: the two-chunk batch and its odd last chunk
+                sv, bank = calls.rows(s, f, s), calls.rows(s, f, 100 + s, unit=True)
+                for classes in (2, 8):
+                    for vn in (None, norm):
+                        res[f'svm_rbf F={f} nvox={nvox} sv={s} classes={classes} voxel_norm={vn is not None} (labels, decisions, workspace)'] = \
+                            same(calls.rbf(x, vn, sv, classes, s + classes))
+                for k in sorted({min(k, s) for k in (1, 4, 5, 20, 32)}):
+                    for weights, it in (('softmax', inv_t), ('uniform', 0.0)):
+                        res[f'knn F={f} nvox={nvox} bank={s} k={k} {weights} (labels, scores, neighbours, similarities, workspace)'] = \
+                            same(calls.knn(x, norm, bank, 8, k, it, s + k))
+    for f in (32, 384):
+        for nvox in (129, 1024):
+            x, _ = calls.volume(f, nvox, 7 + f + nvox)
+            for hidden in ((), (32,), (96, 32)):
+                res[f'mlp F={f} nvox={nvox} hidden={hidden} (labels, logits, probabilities)'] = same(calls.mlp(x, hidden, 6, f + len(hidden)))
+        x, norm = calls.volume(f, 257, 11 + f)
+        res[f'feature_project F={f} nvox=257 k=3 and k=40'] = same(calls.project(x, 3, f)) and same(calls.project(x, 40, f + 1))
+        res[f'kmeans_assign F={f} nvox=257 c=5 and c=40'] = same(calls.assign(x, 5, f)) and same(calls.assign(x, 40, f + 1))
+    for f in (32, 384, 1024):
+        x, norm = calls.volume(f, 129, 13 + f)
+        for vn in (None, norm):
+            res[f'svm_linear F={f} nvox=129 classes=8 voxel_norm={vn is not None} (labels, decisions)'] = same(calls.linear(x, vn, 8, f))
+    return res
+
+
+def classifier_times(libs, dev):
+    """-> {shape: timed(..)} on the shapes of tools/svm_step.py, knn_step.py and mlp_step.py: 64^3 x 384, 1024 rows, 6 classes."""
+    calls, times = Calls(libs, dev, fresh=False), {}
+    f, nvox, s, classes = 384, 64 ** 3, 1024, 6
+    x, norm = calls.volume(f, nvox, 0)
+    quiet = lambda run: (lambda lib: run(lib) and None)       # noqa: E731
+    times[f'svm_rbf 64^3x{f} sv={s}'] = timed(libs, quiet(calls.rbf(x, None, calls.rows(s, f, 1), classes, 2)))
+    times[f'svm_linear 64^3x{f}'] = timed(libs, quiet(calls.linear(x, None, classes, 3)))
+    bank = calls.rows(s, f, 4, unit=True)
+    inv_t = float(torch.tensor(1.0 / 0.07, dtype=torch.float32))
+    for k in (1, 20):
+        times[f'knn 64^3x{f} bank={s} k={k}'] = timed(libs, quiet(calls.knn(x, norm, bank, classes, k, inv_t, 5, outputs=False)))
+    for hidden in ((), (64,), (256,), (256, 256)):
+        times[f'mlp 64^3x{f} hidden={hidden}'] = timed(libs, quiet(calls.mlp(x, hidden, classes, 6)))
+    for f in (32, 128):                                        # knn_step.py's 64^3 x 32 (a _pca32 file), and FP = 128
+        x, norm = calls.volume(f, nvox, f)
+        times[f'svm_rbf 64^3x{f} sv={s}'] = timed(libs, quiet(calls.rbf(x, None, calls.rows(s, f, 1), classes, 2)))
+        bank = calls.rows(s, f, 4, unit=True)
+        for k in (1, 20) if f == 32 else (20,):
+            times[f'knn 64^3x{f} bank={s} k={k}'] = timed(libs, quiet(calls.knn(x, norm, bank, classes, k, inv_t, 5, outputs=False)))
+    return times
+
+
+def classifiers_mode(other, out_json):
+    libs = load_both(other, CLASSIFIER_ENTRIES)
+    dev = torch.device('cuda', 0)
+    return report(classifier_bits(libs, dev), classifier_times(libs, dev), out_json, count_by=lambda case: case.split(' ')[0])
 
 
 def main():
     other = sys.argv[1]
     if len(sys.argv) > 2 and sys.argv[2] == 'attention':
         sys.exit(attention_mode(other, sys.argv[3] if len(sys.argv) > 3 else None, int(sys.argv[4]) if len(sys.argv) > 4 else 256))
+    if len(sys.argv) > 2 and sys.argv[2] == 'classifiers':
+        sys.exit(classifiers_mode(other, sys.argv[3] if len(sys.argv) > 3 else None))
     batch = int(sys.argv[2]) if len(sys.argv) > 2 else 256
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 7
     libs = load_both(other, ('vittf_gemm',))

@@ -1,5 +1,7 @@
-// Row access to an F-major fp16 feature volume [f][nvox] and the score loop over it, shared by the kernels that walk one
-// (pca.hip, kmeans.hip; the reduction along the voxels that the Gram and the cluster sums share is span_rows.h).
+// Row access to an F-major fp16 feature volume [f][nvox], the transposing pickup of its voxels as MFMA B fragments and the
+// score loop over it, shared by the kernels that walk one: pca.hip, kmeans.hip and the linear machine of svm.hip through
+// project_scores, mlp.hip's first contraction and the bank frame of svm.hip and knn.hip (bank_frame.h) through the pickup.
+// (The reduction along the voxels that the Gram and the cluster sums share is span_rows.h.)
 #pragma once
 #include "vittf_common.h"
 
@@ -20,6 +22,26 @@ __device__ __forceinline__ uint4 feat_load8(const unsigned short* __restrict__ r
   return c;
 }
 
+// ---- the transposing pickup (sim_mfma.hip's): feature rows are staged in LDS, ROW bytes apart, 32 voxels of a row per wave.
+// 16-lane group g covers voxels 16 (g & 1) .. + 15 of the wave's 32 and feature group g >> 1; lane 4 q + p of the group
+// addresses row q, voxels 4 p .. 4 p + 3; it receives 4 features of ITS voxel.  tr_lane_offset: the lane's byte offset into
+// the staged rows.  tr_fragment: the B fragment of one MFMA k-step (16 staged rows from `buf` on) of the lane's voxel, two
+// ds_read_b64_tr_b16 four rows apart.  No divergence around it: the transposing read needs all 64 lanes.
+template <int ROW>
+__device__ __forceinline__ int tr_lane_offset(int lane, int wave) {
+  const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
+  return (8 * (grp >> 1) + qq) * ROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
+}
+
+template <int ROW>
+__device__ __forceinline__ s16x8_t tr_fragment(const char* buf) {
+  const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
+  const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * ROW));
+  s16x8_t x;
+  x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
+  return x;
+}
+
 constexpr int FEAT_MAXF = 1024;
 static bool rows_aligned(const void* feat, int64_t nvox) { return nvox % 8 == 0 && ((uintptr_t)feat & 15) == 0; }
 static bool feat_f_ok(int32_t f) { return f >= 32 && f <= FEAT_MAXF && f % 32 == 0; }
@@ -28,9 +50,9 @@ static bool feat_f_ok(int32_t f) { return f >= 32 && f <= FEAT_MAXF && f % 32 ==
 // assignment.  acc[b][r] = sum_f mat[32 b + acc_row(r, h)][f] x[f][v] for voxel v = v0 + 32 wave + lane % 32 (fp32, an
 // accumulator tile per 32-row block; rows >= k are zeros).  The reduction runs over f, so the volume is the operand that
 // needs transposed fragments: the workgroup (512 threads) stages [32 feature rows][256 voxels] parts in LDS and every wave
-// picks the 8 features of its 32 voxels up with ds_read_b64_tr_b16 (sim_mfma.hip's pickup).  The matrix is split into fp16
-// hi + lo halves (mat = hi + lo to 2^-22, sim_mfma_prep's arithmetic) by the workgroup itself, part by part; both stagings
-// are register-prefetched one part ahead.  No divergence in here: the transposing read needs all 64 lanes.
+// picks the 8 features of its 32 voxels up with tr_fragment.  The matrix is split into fp16 hi + lo halves (mat = hi + lo to
+// 2^-22, sim_mfma_prep's arithmetic) by the workgroup itself, part by part; both stagings are register-prefetched one part
+// ahead.  No divergence in here.
 constexpr int PJ_THREADS = 512;
 constexpr int PJ_VOX = 256;                  // voxels per workgroup: 32 per wave
 constexpr int PJ_ROWS = 32;                  // feature rows per staged part: two MFMA k-steps
@@ -62,10 +84,7 @@ __device__ __forceinline__ void project_scores(const unsigned short* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) cpre[j] = (crow < k) ? mat[(int64_t)crow * f + part * PJ_ROWS + 4 * cq + j] : 0.f;
   };
-  // transposing read (sim_mfma.hip): 16-lane group g covers voxels 16 (g & 1) .. + 15 of the wave's 32 and feature group
-  // g >> 1; lane 4 q + p of the group addresses row q, voxels 4 p .. 4 p + 3; it receives 4 features of ITS voxel
-  const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-  const int tr_off = (8 * (grp >> 1) + qq) * PJ_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
+  const int tr_off = tr_lane_offset<PJ_VROW>(lane, wave);
   const int a_off = l31 * PJ_CROW + 16 * h;
 
 #pragma unroll
@@ -96,11 +115,7 @@ __device__ __forceinline__ void project_scores(const unsigned short* __restrict_
     if (part + 1 < parts) prefetch(part + 1);
 #pragma unroll
     for (int s = 0; s < PJ_ROWS / 16; ++s) {
-      const char* buf = vbuf + tr_off + (16 * s) * PJ_VROW;
-      const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
-      const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * PJ_VROW));
-      s16x8_t x;
-      x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
+      const s16x8_t x = tr_fragment<PJ_VROW>(vbuf + tr_off + (16 * s) * PJ_VROW);
 #pragma unroll
       for (int b = 0; b < RB; ++b) {
         const char* cb = cbuf + (32 * b) * PJ_CROW + a_off + 32 * s;

@@ -6,11 +6,9 @@
 // comparison of exactly these fp32 values), rank 1 the nearest; w_j = 1 (uniform) or exp2((sim_j - sim_1) c), c = log2(e) / T;
 // scores[c] = sum of w_j over the ranks j = 1..k of class c, added in fp32 in rank order; label = arg-max, lowest class first.
 //
-// The frame is svm_rbf_kernel's (svm.hip): a workgroup of 4 waves owns 128 voxels, every wave keeps all features of its 32
-// voxels as the B operands of v_mfma_f32_32x32x16_f16 (f padded with zero features to FP = 32, 128, 384 or 768), the bank
-// streams past in chunks of 32 rows -- the prep kernel writes one LDS image per chunk into the workspace: [32 rows][FP] fp16
-// and one 32-bit word per row, (index << 3) | class, 0xffffffff for a row behind the bank -- through a ring of two slots,
-// register-prefetched one chunk ahead.  After the FP / 16 MFMAs of a chunk a lane holds 16 similarities of its OWN voxel
+// The frame is bank_frame.h's, shared with svm_rbf_kernel: the voxels stay where they are as MFMA B operands, the bank streams
+// past in chunks of 32 rows through the ring of LDS images.  An image holds [32 rows][FP] fp16 and one 32-bit word per row,
+// (index << 3) | class, 0xffffffff for a row behind the bank.  After chunk_dots a lane holds 16 similarities of its OWN voxel
 // (rows acc_row(r, h)); lanes l and l + 32 hold the two halves of the chunk.
 //
 // Selection.  Every lane keeps a sorted list of LEN >= k entries (sim, word) of the rows IT has seen, in registers under
@@ -29,47 +27,28 @@
 // under the total order (sim, index): both lanes compute the same entries, of which the first k are the neighbours.
 // Fixed order, no atomics: the same call gives the same bytes, whatever optional outputs are asked for.
 #include "vittf_common.h"
-#include "feat_rows.h"
+#include "bank_frame.h"
 
 namespace {
 
-constexpr int KN_THREADS = 256, KN_WAVES = 4;
-constexpr int KN_VOX = 32 * KN_WAVES;          // voxels per workgroup
-constexpr int KN_CHUNK = 32;                   // bank rows per chunk
-constexpr int KN_VROW = 2 * KN_VOX + 64;       // LDS bytes per staged feature row of the pickup
 constexpr unsigned KN_NONE = 0xffffffffu;      // the word of a row behind the bank / an empty list slot
 
 // image of a chunk: [32 bank rows of 2 FP + 16 bytes][32 words (index << 3) | class]
-__host__ __device__ constexpr int kn_row_bytes(int fp) { return 2 * fp + 16; }
-__host__ __device__ constexpr int kn_image_bytes(int fp) { return KN_CHUNK * kn_row_bytes(fp) + 4 * KN_CHUNK; }
+__host__ __device__ constexpr int kn_image_bytes(int fp) { return BK_CHUNK * bank_row_bytes(fp) + 4 * BK_CHUNK; }
 
-static int knn_padded_f(int32_t f) { return f <= 32 ? 32 : f <= 128 ? 128 : f <= 384 ? 384 : 768; }
-static bool knn_f_ok(int32_t f) { return f >= 32 && f <= 768 && f % 32 == 0; }
 static bool knn_bank_ok(int32_t n) { return n >= 1 && n <= VITTF_KNN_MAX_BANK; }
 
 // grid: chunks.  One image per chunk; rows behind n_bank and features behind f are zeros.
-__global__ __launch_bounds__(KN_THREADS) void knn_prep_kernel(const unsigned short* __restrict__ bank,
+__global__ __launch_bounds__(BK_THREADS) void knn_prep_kernel(const unsigned short* __restrict__ bank,
                                                               const unsigned char* __restrict__ bank_class, int f, int fp,
                                                               int n_bank, char* __restrict__ ws) {
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x;
-  const int rowb = kn_row_bytes(fp);
   char* img = ws + (int64_t)chunk * kn_image_bytes(fp);
-  const int row = tid >> 3, sub = tid & 7;          // 8 threads per bank row, 8 features a step
-  const int s = chunk * KN_CHUNK + row;
-  for (int k8 = sub; k8 < rowb / 16; k8 += 8) {
-    unsigned e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = 8 * k8 + j;
-      e[j] = (s < n_bank && i < f) ? (unsigned)bank[(int64_t)s * f + i] : 0u;
-    }
-    *reinterpret_cast<uint4*>(img + row * rowb + 16 * k8) =
-        make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
-  }
-  if (tid < KN_CHUNK) {
-    const int sm = chunk * KN_CHUNK + tid;
-    reinterpret_cast<unsigned*>(img + KN_CHUNK * rowb)[tid] =
+  bank_write_rows<false>(tid, bank, f, fp, n_bank, chunk, img);
+  if (tid < BK_CHUNK) {
+    const int sm = chunk * BK_CHUNK + tid;
+    reinterpret_cast<unsigned*>(img + BK_CHUNK * bank_row_bytes(fp))[tid] =
         sm < n_bank ? ((unsigned)sm << 3) | (unsigned)(bank_class[sm] & 7) : KN_NONE;
   }
 }
@@ -132,93 +111,86 @@ struct KnnList {
   }
 };
 
+// FP = 32 does not take pickup_fragments, tr_fragment and chunk_dots from the shared headers: there the kernel is all
+// selection (two MFMAs a chunk), and its time follows the order hipcc gives the unrolled insertion chains -- with the
+// helpers, and even with tr_fragment alone, the same instructions came out in another order and k = 4 .. 24 measured 1 to
+// 3 % slower at 64^3 x 32 (k = 20: 0.2972 against 0.2936 ms).  With these lines written out the FP = 32 kernels are within
+// 0.3 % of the code before the frame was shared; the ring helpers cost nothing there and stay.
 template <bool ALIGNED, int FP, int LEN>
-__global__ __launch_bounds__(KN_THREADS) void knn_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
+__global__ __launch_bounds__(BK_THREADS) void knn_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
                                                          const char* __restrict__ images, int chunks, int n_bank, int classes,
                                                          int k, float exp_scale, const float* __restrict__ voxel_norm,
                                                          unsigned char* __restrict__ labels, float* __restrict__ scores,
                                                          int* __restrict__ nn_index, float* __restrict__ nn_sim) {
   constexpr int CAP = LEN <= 1 ? 1 : LEN <= 4 ? 4 : LEN <= 8 ? 8 : LEN <= 16 ? 16 : 32;
-  constexpr int IMG = kn_image_bytes(FP), ROWB = kn_row_bytes(FP);
-  constexpr int PIECES = IMG / 16, PRE = (PIECES + KN_THREADS - 1) / KN_THREADS;
-  static_assert(IMG % 16 == 0, "images are copied in 16-byte pieces");
+  constexpr int IMG = kn_image_bytes(FP);
   __shared__ __attribute__((aligned(16))) char ring[2 * IMG];
-  __shared__ __attribute__((aligned(16))) char vbuf[32 * KN_VROW];
-  __shared__ __attribute__((aligned(4))) unsigned char lab[KN_VOX];
+  __shared__ __attribute__((aligned(16))) char vbuf[32 * BK_VROW];
+  __shared__ __attribute__((aligned(4))) unsigned char lab[BK_VOX];
   // the candidates of BATCH chunks, [row][thread]: a lane reads back only what it wrote itself (any row: no bank conflict)
   constexpr int BATCH = (LEN > 1 && FP == 384) ? 2 : 1;      // (registers leave one workgroup a CU there anyway; 768 lacks the LDS)
-  __shared__ float cand_s[LEN > 1 ? 16 * BATCH * KN_THREADS : 1];
-  __shared__ unsigned cand_m[LEN > 1 ? 16 * BATCH * KN_THREADS : 1];
+  __shared__ float cand_s[LEN > 1 ? 16 * BATCH * BK_THREADS : 1];
+  __shared__ unsigned cand_m[LEN > 1 ? 16 * BATCH * BK_THREADS : 1];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
-  const int64_t v0 = (int64_t)blockIdx.x * KN_VOX;
+  const int64_t v0 = (int64_t)blockIdx.x * BK_VOX;
   const int64_t v = v0 + wave * 32 + l31;
 
-  // the ring: chunk c lies in slot c & 1
-  i32x4_t pre[PRE];
-#define KN_PREFETCH(c) \
-  _Pragma("unroll") for (int j_ = 0; j_ < PRE; ++j_) { \
-    const int i_ = tid + KN_THREADS * j_;   /* the last round is part-filled: its spare lanes load a piece twice */ \
-    pre[j_] = reinterpret_cast<const i32x4_t*>(images + (int64_t)(c) * IMG)[i_ < PIECES ? i_ : PIECES - 1]; \
-  }
-#define KN_COMMIT(c) \
-  _Pragma("unroll") for (int j_ = 0; j_ < PRE; ++j_) { \
-    const int i_ = tid + KN_THREADS * j_; \
-    if (i_ < PIECES) reinterpret_cast<i32x4_t*>(ring + ((c) & 1) * IMG)[i_] = pre[j_]; \
-  }
-  KN_PREFETCH(0)
-
-  // the wave's 32 voxels: all FP features as B fragments (svm_rbf_kernel's transposing pickup, 128 voxels per row)
+  i32x4_t pre[ring_regs(IMG)];
+  ring_prefetch<IMG>(tid, images, 0, pre);
   s16x8_t x[FP / 16];
-  {
+  if constexpr (FP == 32) {
+    // FP = 32 keeps the one-part pickup and the two MFMAs of a chunk written out (see the note above the kernel)
     const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-    const int tr_off = (8 * (grp >> 1) + qq) * KN_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
+    const int tr_off = (8 * (grp >> 1) + qq) * BK_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
 #pragma unroll
-    for (int part = 0; part < FP / 32; ++part) {
-      if (part) __syncthreads();                      // the previous part's fragments have been read
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int i = tid + KN_THREADS * j;
-        const int row = part * 32 + (i >> 4);
-        uint4 c = make_uint4(0u, 0u, 0u, 0u);
-        if (row < f) c = feat_load8<ALIGNED>(feat + (int64_t)row * nvox, v0 + 8 * (i & 15), nvox);
-        *reinterpret_cast<uint4*>(vbuf + (i >> 4) * KN_VROW + 16 * (i & 15)) = c;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const char* buf = vbuf + tr_off + (16 * s) * KN_VROW;
-        const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
-        const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * KN_VROW));
-        s16x8_t t;
-        t[0] = x0[0]; t[1] = x0[1]; t[2] = x0[2]; t[3] = x0[3]; t[4] = x1[0]; t[5] = x1[1]; t[6] = x1[2]; t[7] = x1[3];
-        x[2 * part + s] = t;
-      }
+    for (int j = 0; j < 2; ++j) {
+      const int i = tid + BK_THREADS * j;
+      const int row = i >> 4;
+      uint4 c = make_uint4(0u, 0u, 0u, 0u);
+      if (row < f) c = feat_load8<ALIGNED>(feat + (int64_t)row * nvox, v0 + 8 * (i & 15), nvox);
+      *reinterpret_cast<uint4*>(vbuf + (i >> 4) * BK_VROW + 16 * (i & 15)) = c;
     }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const char* buf = vbuf + tr_off + (16 * s) * BK_VROW;
+      const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
+      const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * BK_VROW));
+      s16x8_t t;
+      t[0] = x0[0]; t[1] = x0[1]; t[2] = x0[2]; t[3] = x0[3]; t[4] = x1[0]; t[5] = x1[1]; t[6] = x1[2]; t[7] = x1[3];
+      x[s] = t;
+    }
+  } else {
+    pickup_fragments<ALIGNED, FP>(tid, feat, f, nvox, v0, vbuf, x);
   }
   const float inv = (voxel_norm && v < nvox) ? 1.f / voxel_norm[v] : 1.f;      // the voxel is x / norm
 
   KnnList<CAP, LEN> best;
   best.clear();
   [[maybe_unused]] unsigned pending = 0u;                                 // bit 16 b + r: row r of the b-th chunk of the batch is a candidate
-  KN_COMMIT(0)
+  ring_commit<IMG>(tid, ring, 0, pre);
   __syncthreads();
   for (int c = 0; c < chunks; ++c) {
-    if (c + 1 < chunks) { KN_PREFETCH(c + 1) }
+    if (c + 1 < chunks) ring_prefetch<IMG>(tid, images, c + 1, pre);
     const char* slot = ring + (c & 1) * IMG;
-    const unsigned* word = reinterpret_cast<const unsigned*>(slot + KN_CHUNK * ROWB);
+    const unsigned* word = reinterpret_cast<const unsigned*>(slot + BK_CHUNK * bank_row_bytes(FP));
     f32x16_t acc;
+    if constexpr (FP == 32) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const char* ab = slot + l31 * ROWB + 16 * h;
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      const char* ab = slot + l31 * bank_row_bytes(FP) + 16 * h;
 #pragma unroll
-    for (int kk = 0; kk < FP / 16; ++kk) acc = mfma32<VITTF_FP16>(*reinterpret_cast<const s16x8_t*>(ab + 32 * kk), x[kk], acc);
+      for (int kk = 0; kk < FP / 16; ++kk) acc = mfma32<VITTF_FP16>(*reinterpret_cast<const s16x8_t*>(ab + 32 * kk), x[kk], acc);
+    } else {
+      acc = chunk_dots<FP>(l31, h, slot, x);
+    }
     float sim[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) sim[r] = acc[r] * inv;
     if (c == chunks - 1) {                                // rows behind the bank are never neighbours
-      const int left = n_bank - KN_CHUNK * c;
+      const int left = n_bank - BK_CHUNK * c;
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (acc_row(r, h) >= left) sim[r] = -__builtin_inff();
@@ -247,8 +219,8 @@ __global__ __launch_bounds__(KN_THREADS) void knn_kernel(const unsigned short* _
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * q + i;
-          cand_s[(base + r) * KN_THREADS + tid] = sim[r];
-          cand_m[(base + r) * KN_THREADS + tid] = (unsigned)w4[i];
+          cand_s[(base + r) * BK_THREADS + tid] = sim[r];
+          cand_m[(base + r) * BK_THREADS + tid] = (unsigned)w4[i];
           pending |= sim[r] > kth ? 1u << (base + r) : 0u;
         }
       }
@@ -257,18 +229,16 @@ __global__ __launch_bounds__(KN_THREADS) void knn_kernel(const unsigned short* _
       if (BATCH == 1 || (c & 1) || c == chunks - 1) {
         while (__any(pending != 0u)) {
           const int pick = pending ? __builtin_ctz(pending) : 0;             // ascending index order
-          const float cs = pending ? cand_s[pick * KN_THREADS + tid] : -__builtin_inff();
-          const unsigned cm = cand_m[pick * KN_THREADS + tid];
+          const float cs = pending ? cand_s[pick * BK_THREADS + tid] : -__builtin_inff();
+          const unsigned cm = cand_m[pick * BK_THREADS + tid];
           pending &= pending - 1u;
           best.insert(cs, cm);
         }
       }
     }
-    if (c + 1 < chunks) { KN_COMMIT(c + 1) }              // slot (c + 1) & 1 was last read before the previous barrier
+    if (c + 1 < chunks) ring_commit<IMG>(tid, ring, c + 1, pre);      // slot (c + 1) & 1 was last read before the previous barrier
     __syncthreads();
   }
-#undef KN_PREFETCH
-#undef KN_COMMIT
 
   // both lanes of a voxel: the merged list, the weights and the per-class sums in rank order
   if constexpr (CAP == 1) {
@@ -309,7 +279,7 @@ __global__ __launch_bounds__(KN_THREADS) void knn_kernel(const unsigned short* _
   }
   if (h == 0) lab[wave * 32 + l31] = (unsigned char)bi;
   __syncthreads();
-  if (tid < KN_VOX / 4) {
+  if (tid < BK_VOX / 4) {
     const int64_t vq = v0 + 4 * tid;
     if ((((uintptr_t)labels) & 3) == 0 && vq + 3 < nvox) {
       *reinterpret_cast<unsigned*>(labels + vq) = *reinterpret_cast<const unsigned*>(lab + 4 * tid);
@@ -324,9 +294,9 @@ __global__ __launch_bounds__(KN_THREADS) void knn_kernel(const unsigned short* _
 }  // namespace
 
 size_t vittf_knn_workspace_bytes(int32_t f, int32_t n_bank) {
-  if (!knn_f_ok(f) || !knn_bank_ok(n_bank)) return 0;
-  const size_t chunks = ((size_t)n_bank + KN_CHUNK - 1) / KN_CHUNK;
-  return chunks * (size_t)kn_image_bytes(knn_padded_f(f));
+  if (!bank_f_ok(f) || !knn_bank_ok(n_bank)) return 0;
+  const size_t chunks = ((size_t)n_bank + BK_CHUNK - 1) / BK_CHUNK;
+  return chunks * (size_t)kn_image_bytes(bank_padded_f(f));
 }
 
 int vittf_knn_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint16_t* bank, const uint8_t* bank_class,
@@ -334,24 +304,24 @@ int vittf_knn_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint16
                      uint8_t* labels, float* scores, int32_t* nn_index, float* nn_sim, void* ws, size_t ws_bytes,
                      void* stream) {
   if (!feat || !bank || !bank_class || !labels || !ws) return VITTF_ERR_INVALID_ARG;
-  if (!knn_f_ok(f) || nvox < 1 || !knn_bank_ok(n_bank) || classes < 2 || classes > VITTF_KNN_MAX_CLASSES || k < 1 ||
+  if (!bank_f_ok(f) || nvox < 1 || !knn_bank_ok(n_bank) || classes < 2 || classes > VITTF_KNN_MAX_CLASSES || k < 1 ||
       k > VITTF_KNN_MAX_K || k > n_bank || !(inv_temperature >= 0.f) || !(inv_temperature < __builtin_inff()))
     return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)bank & 1) || ((uintptr_t)voxel_norm & 3) || ((uintptr_t)scores & 3) ||
       ((uintptr_t)nn_index & 3) || ((uintptr_t)nn_sim & 3) || ((uintptr_t)ws & 15))
     return VITTF_ERR_INVALID_ARG;
-  const int64_t wgs = (nvox + KN_VOX - 1) / KN_VOX;
+  const int64_t wgs = (nvox + BK_VOX - 1) / BK_VOX;
   if (wgs > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
   if (ws_bytes < vittf_knn_workspace_bytes(f, n_bank)) return VITTF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const int chunks = (n_bank + KN_CHUNK - 1) / KN_CHUNK;
-  const int fp = knn_padded_f(f);
+  const int chunks = (n_bank + BK_CHUNK - 1) / BK_CHUNK;
+  const int fp = bank_padded_f(f);
   const float exp_scale = (float)((double)inv_temperature * 1.4426950408889634074);     // exp(d / T) = exp2(d exp_scale)
   if (inv_temperature > 0.f && !(exp_scale > 0.f && exp_scale < __builtin_inff())) return VITTF_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)chunks), dim3(KN_THREADS), 0, st, bank, bank_class, f, fp, n_bank, (char*)ws);
+  hipLaunchKernelGGL(knn_prep_kernel, dim3((unsigned)chunks), dim3(BK_THREADS), 0, st, bank, bank_class, f, fp, n_bank, (char*)ws);
   const bool al = rows_aligned(feat, nvox);
 #define KN_LAUNCH(AL, FPV, CAPV) \
-  hipLaunchKernelGGL((knn_kernel<AL, FPV, CAPV>), dim3((unsigned)wgs), dim3(KN_THREADS), 0, st, feat, f, nvox, (const char*)ws, chunks, \
+  hipLaunchKernelGGL((knn_kernel<AL, FPV, CAPV>), dim3((unsigned)wgs), dim3(BK_THREADS), 0, st, feat, f, nvox, (const char*)ws, chunks, \
                      n_bank, classes, k, exp_scale, voxel_norm, labels, scores, nn_index, nn_sim)
 #define KN_CAP(AL, FPV) do { if (k == 1) KN_LAUNCH(AL, FPV, 1); else if (k <= 4) KN_LAUNCH(AL, FPV, 4); else if (k <= 8) KN_LAUNCH(AL, FPV, 8); \
                              else if (k <= 16) KN_LAUNCH(AL, FPV, 16); else if (k <= 20) KN_LAUNCH(AL, FPV, 20); \

@@ -160,8 +160,7 @@ __device__ __forceinline__ void first_contract(const unsigned short* __restrict_
       cpre[j] = reinterpret_cast<const i32x4_t*>(img + (int64_t)part * pieces * 16)[i < pieces ? i : pieces - 1];
     }
   };
-  const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-  const int tr_off = (8 * (grp >> 1) + qq) * ML_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
+  const int tr_off = tr_lane_offset<ML_VROW>(lane, wave);
   const int a_off = l31 * ML_CROW + 16 * h;
 #pragma unroll
   for (int b = 0; b < RB; ++b)
@@ -185,11 +184,7 @@ __device__ __forceinline__ void first_contract(const unsigned short* __restrict_
     if (part + 1 < parts) prefetch(part + 1);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const char* buf = vbuf + tr_off + (16 * s) * ML_VROW;
-      const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
-      const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * ML_VROW));
-      s16x8_t x;
-      x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
+      const s16x8_t x = tr_fragment<ML_VROW>(vbuf + tr_off + (16 * s) * ML_VROW);
 #pragma unroll
       for (int b = 0; b < RB; ++b) {
         if (b < nb) {

@@ -3,14 +3,11 @@
 // ..., (C-2,C-1); dec_p > 0 votes for i, anything else for j; the class with the most votes wins, the lowest index among
 // equal counts.
 //
-// vittf_svm_rbf_decide: dec_p(x) = sum_s coef[p][s] exp(-gamma |x - sv_s|^2) + b_p.  The voxels stay where they are: a
-// workgroup of 4 waves owns 128 voxels, every wave picks all features of its 32 voxels up once (ds_read_b64_tr_b16 from
-// staged feature rows, feat_rows.h's pickup) and keeps them as the B operands of v_mfma_f32_32x32x16_f16, f padded with zero
-// features to FP = 32, 128, 384 or 768.  The support vectors stream past in chunks of 32: the prep kernel writes one LDS
-// image per chunk into the workspace -- [32 sv][FP] fp16 rows (the support vectors ARE fp16: no split), the chunk's
-// coefficients as fp16 hi + lo A fragments, and |sv|^2 in fp32 -- and the workgroups copy the images through a ring of two
-// slots, register-prefetched one chunk ahead.  Per chunk and wave:
-//   1. acc[sv][voxel] = sv . x                                     FP / 16 MFMAs, fp32 accumulation of exact products
+// vittf_svm_rbf_decide: dec_p(x) = sum_s coef[p][s] exp(-gamma |x - sv_s|^2) + b_p on the frame of bank_frame.h: the voxels
+// stay where they are as MFMA B operands, the support vectors stream past in chunks of 32 through the ring of LDS images.  An
+// image holds [32 sv][FP] fp16 rows (the support vectors ARE fp16: no split), the chunk's coefficients as fp16 hi + lo A
+// fragments, and |sv|^2 in fp32.  Per chunk and wave:
+//   1. acc[sv][voxel] = sv . x                                     chunk_dots
 //   2. d2 = max(|x|^2 + |sv|^2 - 2 sv . x, 0);  K = exp2(-gamma log2(e) d2)         (|x|^2 from the wave's own registers)
 //   3. the accumulator tile holds 16 support-vector rows of the lane's OWN voxel: K (as fp16 hi + lo, 2^-22) is a B operand
 //      as it lies, with the k index of the second contraction permuted to the accumulator's row order -- the prep kernel
@@ -27,25 +24,18 @@
 // and l + 32 the two halves; eight 4-bit vote counters share one 32-bit word, one __shfl_xor(.., 32) and one add combine the
 // halves.  The decisions are written (when asked for) from the very registers the vote reads.
 #include "vittf_common.h"
-#include "feat_rows.h"
+#include "bank_frame.h"
 
 namespace {
 
 constexpr int SVM_MAX_PAIRS = VITTF_SVM_MAX_CLASSES * (VITTF_SVM_MAX_CLASSES - 1) / 2;    // 28 <= 32: one accumulator tile
-constexpr int SV_THREADS = 256, SV_WAVES = 4;
-constexpr int SV_VOX = 32 * SV_WAVES;          // voxels per workgroup of the RBF kernel
-constexpr int SV_CHUNK = 32;                   // support vectors per chunk
-constexpr int SV_VROW = 2 * SV_VOX + 64;       // LDS bytes per staged feature row of the pickup
-constexpr int SV_CROW = 2 * SV_CHUNK + 16;     // LDS bytes per coefficient row (hi or lo) of a chunk
+constexpr int SV_CROW = 2 * BK_CHUNK + 16;     // LDS bytes per coefficient row (hi or lo) of a chunk
 constexpr int SV_HEADER = 256;                 // workspace bytes in front of the images: {scale, 1 / scale}
 static_assert(SVM_MAX_PAIRS <= 32, "the decisions of a voxel fill one 32-row tile");
 
 // image of a chunk: [32 sv rows of 2 FP + 16 bytes][32 coefficient rows hi][32 lo][32 x |sv|^2 fp32]
-__host__ __device__ constexpr int sv_row_bytes(int fp) { return 2 * fp + 16; }
-__host__ __device__ constexpr int sv_image_bytes(int fp) { return SV_CHUNK * sv_row_bytes(fp) + 2 * 32 * SV_CROW + 4 * SV_CHUNK; }
+__host__ __device__ constexpr int sv_image_bytes(int fp) { return BK_CHUNK * bank_row_bytes(fp) + 2 * 32 * SV_CROW + 4 * BK_CHUNK; }
 
-static int svm_padded_f(int32_t f) { return f <= 32 ? 32 : f <= 128 ? 128 : f <= 384 ? 384 : 768; }
-static bool svm_rbf_f_ok(int32_t f) { return f >= 32 && f <= 768 && f % 32 == 0; }
 static bool svm_classes_ok(int32_t c) { return c >= 2 && c <= VITTF_SVM_MAX_CLASSES; }
 static bool svm_nsv_ok(int32_t n) { return n >= 1 && n <= VITTF_SVM_MAX_SV; }
 
@@ -144,113 +134,57 @@ __global__ __launch_bounds__(1024) void svm_scale_kernel(const float* __restrict
 }
 
 // grid: chunks.  One image per chunk (see sv_image_bytes); rows behind n_sv and features behind f are zeros.
-__global__ __launch_bounds__(SV_THREADS) void svm_prep_kernel(const unsigned short* __restrict__ sv, int f, int fp, int n_sv,
+__global__ __launch_bounds__(BK_THREADS) void svm_prep_kernel(const unsigned short* __restrict__ sv, int f, int fp, int n_sv,
                                                               const float* __restrict__ coef, int pairs, char* __restrict__ ws) {
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x;
-  const int rowb = sv_row_bytes(fp);
   char* img = ws + SV_HEADER + (int64_t)chunk * sv_image_bytes(fp);
   const float inv_scale = reinterpret_cast<const float*>(ws)[1];
-  // rows: 8 threads per support vector, 8 features a step; |sv|^2 in a fixed order (strided partial sums, then a tree)
-  const int row = tid >> 3, sub = tid & 7;
-  const int s = chunk * SV_CHUNK + row;
-  float sq = 0.f;
-  for (int k8 = sub; k8 < rowb / 16; k8 += 8) {
-    unsigned short e[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = 8 * k8 + j;
-      e[j] = (s < n_sv && i < f) ? sv[(int64_t)s * f + i] : (unsigned short)0;
-      const float x = f16bits_to_f32(e[j]);
-      sq = fmaf(x, x, sq);
-    }
-    *reinterpret_cast<uint4*>(img + row * rowb + 16 * k8) =
-        make_uint4(e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16), e[4] | ((unsigned)e[5] << 16), e[6] | ((unsigned)e[7] << 16));
-  }
+  float sq = bank_write_rows<true>(tid, sv, f, fp, n_sv, chunk, img);     // |sv|^2: the strided partial sums, then a tree
   sq += __shfl_xor(sq, 1);
   sq += __shfl_xor(sq, 2);
   sq += __shfl_xor(sq, 4);
-  char* cimg = img + SV_CHUNK * rowb;
-  if (sub == 0) reinterpret_cast<float*>(cimg + 2 * 32 * SV_CROW)[row] = sq;
+  char* cimg = img + BK_CHUNK * bank_row_bytes(fp);
+  if ((tid & 7) == 0) reinterpret_cast<float*>(cimg + 2 * 32 * SV_CROW)[tid >> 3] = sq;
   // coefficients: pair row p, k-step ks, lane half h, element j <-> support vector acc_row(8 ks + j, h) of the chunk
-  for (int i = tid; i < 32 * 32; i += SV_THREADS) {
+  for (int i = tid; i < 32 * 32; i += BK_THREADS) {
     const int p = i >> 5, q = i & 31;
     const int ks = q >> 4, h = (q >> 3) & 1, j = q & 7;
-    const int sidx = chunk * SV_CHUNK + acc_row(8 * ks + j, h);
+    const int sidx = chunk * BK_CHUNK + acc_row(8 * ks + j, h);
     const float c = (p < pairs && sidx < n_sv) ? coef[(int64_t)p * n_sv + sidx] * inv_scale : 0.f;
     const unsigned short hi = f32_to_f16bits(c);
     const unsigned short lo = f32_to_f16bits(c - f16bits_to_f32(hi));
     *reinterpret_cast<unsigned short*>(cimg + p * SV_CROW + 2 * q) = hi;
     *reinterpret_cast<unsigned short*>(cimg + 32 * SV_CROW + p * SV_CROW + 2 * q) = lo;
   }
-  for (int i = tid; i < 2 * 32; i += SV_THREADS)      // the 16 bytes behind every coefficient row
-    *reinterpret_cast<uint4*>(cimg + i * SV_CROW + 2 * SV_CHUNK) = make_uint4(0u, 0u, 0u, 0u);
+  for (int i = tid; i < 2 * 32; i += BK_THREADS)      // the 16 bytes behind every coefficient row
+    *reinterpret_cast<uint4*>(cimg + i * SV_CROW + 2 * BK_CHUNK) = make_uint4(0u, 0u, 0u, 0u);
 }
 
 // ------------------------------------------------------------------------------------------------ RBF: the decision
 template <bool ALIGNED, int FP>
-__global__ __launch_bounds__(SV_THREADS) void svm_rbf_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
+__global__ __launch_bounds__(BK_THREADS) void svm_rbf_kernel(const unsigned short* __restrict__ feat, int f, int64_t nvox,
                                                              const char* __restrict__ ws, int chunks,
                                                              const float* __restrict__ intercept, int classes, float neg_g2,
                                                              const float* __restrict__ voxel_norm,
                                                              unsigned char* __restrict__ labels, float* __restrict__ decision) {
-  constexpr int IMG = sv_image_bytes(FP), ROWB = sv_row_bytes(FP);
-  constexpr int PIECES = IMG / 16, PRE = (PIECES + SV_THREADS - 1) / SV_THREADS;
-  static_assert(IMG % 16 == 0, "images are copied in 16-byte pieces");
+  constexpr int IMG = sv_image_bytes(FP);
   __shared__ __attribute__((aligned(16))) char ring[2 * IMG];
-  __shared__ __attribute__((aligned(16))) char vbuf[32 * SV_VROW];
-  __shared__ __attribute__((aligned(4))) unsigned char lab[SV_VOX];
+  __shared__ __attribute__((aligned(16))) char vbuf[32 * BK_VROW];
+  __shared__ __attribute__((aligned(4))) unsigned char lab[BK_VOX];
   __shared__ unsigned char tab[32];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, l31 = lane & 31;
-  const int64_t v0 = (int64_t)blockIdx.x * SV_VOX;
+  const int64_t v0 = (int64_t)blockIdx.x * BK_VOX;
   const int64_t v = v0 + wave * 32 + l31;
   pair_table(tab, classes);
 
-  // the ring: chunk c lies in slot c & 1
   const char* images = ws + SV_HEADER;
-  i32x4_t pre[PRE];                                  // (a native vector: hipcc keeps an array of HIP uint4 structs in scratch here)
-#define SV_PREFETCH(c) \
-  _Pragma("unroll") for (int j_ = 0; j_ < PRE; ++j_) { \
-    const int i_ = tid + SV_THREADS * j_;   /* the last round is part-filled: its spare lanes load a piece twice */ \
-    pre[j_] = reinterpret_cast<const i32x4_t*>(images + (int64_t)(c) * IMG)[i_ < PIECES ? i_ : PIECES - 1]; \
-  }
-#define SV_COMMIT(c) \
-  _Pragma("unroll") for (int j_ = 0; j_ < PRE; ++j_) { \
-    const int i_ = tid + SV_THREADS * j_; \
-    if (i_ < PIECES) reinterpret_cast<i32x4_t*>(ring + ((c) & 1) * IMG)[i_] = pre[j_]; \
-  }
-  SV_PREFETCH(0)
-
-  // the wave's 32 voxels: all FP features as B fragments (project_scores' transposing pickup, 128 voxels per row)
+  i32x4_t pre[ring_regs(IMG)];
+  ring_prefetch<IMG>(tid, images, 0, pre);
   s16x8_t x[FP / 16];
-  {
-    const int grp = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
-    const int tr_off = (8 * (grp >> 1) + qq) * SV_VROW + 2 * (wave * 32 + 16 * (grp & 1) + 4 * pp);
-#pragma unroll
-    for (int part = 0; part < FP / 32; ++part) {
-      if (part) __syncthreads();                      // the previous part's fragments have been read
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int i = tid + SV_THREADS * j;
-        const int row = part * 32 + (i >> 4);
-        uint4 c = make_uint4(0u, 0u, 0u, 0u);
-        if (row < f) c = feat_load8<ALIGNED>(feat + (int64_t)row * nvox, v0 + 8 * (i & 15), nvox);
-        *reinterpret_cast<uint4*>(vbuf + (i >> 4) * SV_VROW + 16 * (i & 15)) = c;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const char* buf = vbuf + tr_off + (16 * s) * SV_VROW;
-        const s16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf));
-        const s16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(buf + 4 * SV_VROW));
-        s16x8_t t;
-        t[0] = x0[0]; t[1] = x0[1]; t[2] = x0[2]; t[3] = x0[3]; t[4] = x1[0]; t[5] = x1[1]; t[6] = x1[2]; t[7] = x1[3];
-        x[2 * part + s] = t;
-      }
-    }
-  }
+  pickup_fragments<ALIGNED, FP>(tid, feat, f, nvox, v0, vbuf, x);
   // |x|^2 of the lane's voxel: its half of the features in register order, then the other half's sum
   float x2 = 0.f;
 #pragma unroll
@@ -269,18 +203,13 @@ __global__ __launch_bounds__(SV_THREADS) void svm_rbf_kernel(const unsigned shor
   f32x16_t dec;
 #pragma unroll
   for (int r = 0; r < 16; ++r) dec[r] = 0.f;
-  SV_COMMIT(0)
+  ring_commit<IMG>(tid, ring, 0, pre);
   __syncthreads();
   for (int c = 0; c < chunks; ++c) {
-    if (c + 1 < chunks) { SV_PREFETCH(c + 1) }
+    if (c + 1 < chunks) ring_prefetch<IMG>(tid, images, c + 1, pre);
     const char* slot = ring + (c & 1) * IMG;
-    const char* cimg = slot + SV_CHUNK * ROWB;
-    f32x16_t acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    const char* ab = slot + l31 * ROWB + 16 * h;
-#pragma unroll
-    for (int k = 0; k < FP / 16; ++k) acc = mfma32<VITTF_FP16>(*reinterpret_cast<const s16x8_t*>(ab + 32 * k), x[k], acc);
+    const char* cimg = slot + BK_CHUNK * bank_row_bytes(FP);
+    const f32x16_t acc = chunk_dots<FP>(l31, h, slot, x);
     // K of the lane's voxel against its 16 support-vector rows, as B fragments in accumulator order
     s16x8_t kh[2], kl[2];
     const float* s2 = reinterpret_cast<const float*>(cimg + 2 * 32 * SV_CROW);
@@ -306,44 +235,42 @@ __global__ __launch_bounds__(SV_THREADS) void svm_rbf_kernel(const unsigned shor
       dec = mfma32<VITTF_FP16>(ch, kl[s], dec);
       dec = mfma32<VITTF_FP16>(cl, kh[s], dec);
     }
-    if (c + 1 < chunks) { SV_COMMIT(c + 1) }              // slot (c + 1) & 1 was last read before the previous barrier
+    if (c + 1 < chunks) ring_commit<IMG>(tid, ring, c + 1, pre);      // slot (c + 1) & 1 was last read before the previous barrier
     __syncthreads();
   }
-#undef SV_PREFETCH
-#undef SV_COMMIT
-  vote_epilogue<SV_VOX>(dec, scale, intercept, classes, tab, lab, v0, nvox, labels, decision);
+  vote_epilogue<BK_VOX>(dec, scale, intercept, classes, tab, lab, v0, nvox, labels, decision);
 }
 
 }  // namespace
 
 size_t vittf_svm_rbf_workspace_bytes(int32_t f, int32_t n_sv, int32_t classes) {
-  if (!svm_rbf_f_ok(f) || !svm_nsv_ok(n_sv) || !svm_classes_ok(classes)) return 0;
-  const size_t chunks = ((size_t)n_sv + SV_CHUNK - 1) / SV_CHUNK;
-  return SV_HEADER + chunks * (size_t)sv_image_bytes(svm_padded_f(f));
+  if (!bank_f_ok(f) || !svm_nsv_ok(n_sv) || !svm_classes_ok(classes)) return 0;
+  const size_t chunks = ((size_t)n_sv + BK_CHUNK - 1) / BK_CHUNK;
+  return SV_HEADER + chunks * (size_t)sv_image_bytes(bank_padded_f(f));
 }
 
 int vittf_svm_rbf_decide(const uint16_t* feat, int32_t f, int64_t nvox, const uint16_t* sv, const float* pair_coef,
                          const float* intercept, int32_t n_sv, int32_t classes, float gamma, const float* voxel_norm,
                          uint8_t* labels, float* decision, void* ws, size_t ws_bytes, void* stream) {
   if (!feat || !sv || !pair_coef || !intercept || !labels || !ws) return VITTF_ERR_INVALID_ARG;
-  if (!svm_rbf_f_ok(f) || nvox < 1 || !svm_nsv_ok(n_sv) || !svm_classes_ok(classes) || !(gamma >= 0.f) || !(gamma < __builtin_inff()))
+  if (!bank_f_ok(f) || nvox < 1 || !svm_nsv_ok(n_sv) || !svm_classes_ok(classes) || !(gamma >= 0.f) || !(gamma < __builtin_inff()))
     return VITTF_ERR_INVALID_ARG;
   if (((uintptr_t)feat & 1) || ((uintptr_t)sv & 1) || ((uintptr_t)pair_coef & 3) || ((uintptr_t)intercept & 3) ||
       ((uintptr_t)voxel_norm & 3) || ((uintptr_t)decision & 3) || ((uintptr_t)ws & 15))
     return VITTF_ERR_INVALID_ARG;
-  const int64_t wgs = (nvox + SV_VOX - 1) / SV_VOX;
+  const int64_t wgs = (nvox + BK_VOX - 1) / BK_VOX;
   if (wgs > 0x7fffffff) return VITTF_ERR_INVALID_ARG;
   if (ws_bytes < vittf_svm_rbf_workspace_bytes(f, n_sv, classes)) return VITTF_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int pairs = classes * (classes - 1) / 2;
-  const int chunks = (n_sv + SV_CHUNK - 1) / SV_CHUNK;
-  const int fp = svm_padded_f(f);
+  const int chunks = (n_sv + BK_CHUNK - 1) / BK_CHUNK;
+  const int fp = bank_padded_f(f);
   const float neg_g2 = (float)(-(double)gamma * 1.4426950408889634074);     // exp(-gamma d2) = exp2(neg_g2 d2)
   hipLaunchKernelGGL(svm_scale_kernel, dim3(1), dim3(1024), 0, st, pair_coef, (int64_t)pairs * n_sv, (float*)ws);
-  hipLaunchKernelGGL(svm_prep_kernel, dim3((unsigned)chunks), dim3(SV_THREADS), 0, st, sv, f, fp, n_sv, pair_coef, pairs, (char*)ws);
+  hipLaunchKernelGGL(svm_prep_kernel, dim3((unsigned)chunks), dim3(BK_THREADS), 0, st, sv, f, fp, n_sv, pair_coef, pairs, (char*)ws);
   const bool al = rows_aligned(feat, nvox);
 #define SV_LAUNCH(AL, FPV) \
-  hipLaunchKernelGGL((svm_rbf_kernel<AL, FPV>), dim3((unsigned)wgs), dim3(SV_THREADS), 0, st, feat, f, nvox, (const char*)ws, chunks, \
+  hipLaunchKernelGGL((svm_rbf_kernel<AL, FPV>), dim3((unsigned)wgs), dim3(BK_THREADS), 0, st, feat, f, nvox, (const char*)ws, chunks, \
                      intercept, classes, neg_g2, voxel_norm, labels, decision)
 #define SV_PICK(FPV) do { if (al) SV_LAUNCH(true, FPV); else SV_LAUNCH(false, FPV); } while (0)
   if (fp == 32) SV_PICK(32); else if (fp == 128) SV_PICK(128); else if (fp == 384) SV_PICK(384); else SV_PICK(768);

@@ -18,14 +18,11 @@ Three rules make the forest exact and safe:
   * trees are stored in topological order (left > i and right > i for every inner node i) and the walk is bounded by
     max_depth, the depth of the deepest tree: validate() refuses everything else on the host, before any upload.
 """
-import zipfile
-
 import numpy as np
 import torch
 
-from . import _lib
-from ._featvol import _as_matrix, _np, _on_device
-from .svm import round_samples, sample                              # noqa: F401  (the training rows are drawn as the SVM's)
+from . import _classify, _lib
+from ._classify import round_samples, sample                        # noqa: F401  (the training rows of every classifier)
 
 FORMAT = 'vittf-forest-1'
 
@@ -58,6 +55,7 @@ class ForestModel:
     The constructor validates (see validate)."""
     ARRAYS = ('format', 'class_names', 'labels', 'n_features', 'tree_offset', 'feature', 'threshold', 'left', 'right', 'value',
               'fit_time')
+    normalize = False                                                 # thresholds on single features: no geometry to normalise
 
     def __init__(self, class_names, labels, n_features, tree_offset, feature, threshold, left, right, value, fit_time=0.0):
         self.class_names = [str(n) for n in class_names]
@@ -90,12 +88,8 @@ class ForestModel:
         roots the child of exactly one node, features in 0..F-1, no NaN threshold.  What passes cannot make a walk leave its
         tree or run longer than the depth returned."""
         c, f = self.classes, self.n_features
-        if not 2 <= c <= _lib.FOREST_MAX_CLASSES:
-            raise ValueError(f'classes must be in 2..{_lib.FOREST_MAX_CLASSES}, got {c}')
-        if len(self.class_names) != c or np.any(np.diff(self.labels.astype(np.int64)) <= 0):
-            raise ValueError('class_names and labels must hold one entry per class, the labels ascending')
-        if f % 32 or not 32 <= f <= 1024:
-            raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
+        _classify.check_classes(self.class_names, self.labels, _lib.FOREST_MAX_CLASSES)
+        _classify.check_f(f)
         off = self.tree_offset
         t = off.size - 1
         if not 1 <= t <= _lib.FOREST_MAX_TREES:
@@ -139,6 +133,10 @@ class ForestModel:
                 raise ValueError(f'a tree is deeper than {_lib.FOREST_MAX_DEPTH}')
             frontier = np.concatenate([self.left[fi] + off[tree[fi]], self.right[fi] + off[tree[fi]]])
         return depth
+
+    def decide_slab(self, x, want_extra):
+        """(labels, the uint32 votes [C][n] or None) of the (F, n) matrix x."""
+        return decide(x, self, want_extra)
 
 
 # ---------------------------------------------------------------------------------------------- the fit (fp64, host)
@@ -229,18 +227,9 @@ def fit(samples, targets, trees=256, max_features='sqrt', max_depth=None, min_sa
     t0 = time.time()
     x16 = round_samples(samples)
     x = x16.astype(np.float64)
-    t = _np(targets, np.int64).reshape(-1)
     n, f = x.shape
-    if t.size != n:
-        raise ValueError(f'{t.size} targets for {n} samples')
-    if f % 32 or not 32 <= f <= 1024:
-        raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
-    if n and (t.min() < 0 or t.max() > 255):
-        raise ValueError('targets must be label values in 0..255')
-    values, y = np.unique(t, return_inverse=True)
+    values, y, names = _classify.class_table(targets, class_names, n, _lib.FOREST_MAX_CLASSES, f)
     c = values.size
-    if not 2 <= c <= _lib.FOREST_MAX_CLASSES:
-        raise ValueError(f'classes must be in 2..{_lib.FOREST_MAX_CLASSES}, got {c}')
     if not 1 <= int(trees) <= _lib.FOREST_MAX_TREES:
         raise ValueError(f'trees must number 1..{_lib.FOREST_MAX_TREES}, got {trees}')
     if max_depth is not None and not 1 <= int(max_depth) <= _lib.FOREST_MAX_DEPTH:
@@ -248,9 +237,7 @@ def fit(samples, targets, trees=256, max_features='sqrt', max_depth=None, min_sa
     if not int(min_samples_leaf) >= 1:
         raise ValueError(f'min_samples_leaf must be at least 1, got {min_samples_leaf}')
     k = _n_candidates(max_features, f)
-    names = [str(v) for v in values] if class_names is None else [str(s) for s in class_names]
-    if len(names) != c:
-        raise ValueError(f'{len(names)} class names for {c} classes')
+    _classify.check_names(names, c)
     parts = []
     for tr in range(int(trees)):
         rng = np.random.default_rng([int(seed), tr])
@@ -342,40 +329,20 @@ def save_model(model, path):
 
 def is_forest_file(path):
     """True when `path` is an .npz that names itself a forest model (the command line picks the classifier of --model by it)."""
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            return 'format' in z.files and str(z['format'][()]) == FORMAT
-    except Exception:
-        return False
+    return _classify.file_format(path) == FORMAT
 
 
 def load_model(path):
     """The ForestModel of a file save_model wrote; ValueError for anything else (an SVM model file, a missing key, arrays that
     validate() refuses, another .npz, a .npy, a damaged file)."""
-    try:
-        z = np.load(path, allow_pickle=False)
-    except zipfile.BadZipFile as e:
-        raise ValueError(f'{path} is not a readable .npz: {e}') from None
-    if not isinstance(z, np.lib.npyio.NpzFile):
-        raise ValueError(f'{path} is not an .npz of a forest model')
-    with z:
-        if 'sv' in z.files and 'pair_coef' in z.files:
-            raise ValueError(f'{path} is an SVM model file, not a forest (vt.svm.load_model reads it)')
-        missing = sorted(set(ForestModel.ARRAYS) - set(z.files))
-        if missing:
-            raise ValueError(f'{path} is not a forest model file: it lacks {missing}')
-        try:
-            if str(z['format'][()]) != FORMAT:
-                raise ValueError(f"format {str(z['format'][()])!r} is not {FORMAT!r}")
-            dtypes = {'labels': np.uint8, 'tree_offset': np.int64, 'feature': np.int32, 'threshold': np.float16, 'left': np.int32,
-                      'right': np.int32, 'value': np.uint16}
-            for k, dt in dtypes.items():
-                if z[k].dtype != dt:
-                    raise ValueError(f'{k} is {z[k].dtype}, not {np.dtype(dt)}')
-            return ForestModel([str(s) for s in z['class_names'].reshape(-1)], z['labels'], int(z['n_features']), z['tree_offset'],
-                               z['feature'], z['threshold'], z['left'], z['right'], z['value'], float(z['fit_time']))
-        except (TypeError, IndexError) as e:
-            raise ValueError(f'{path} is not a forest model file: {e}') from None
+    dtypes = {'labels': np.uint8, 'tree_offset': np.int64, 'feature': np.int32, 'threshold': np.float16, 'left': np.int32,
+              'right': np.int32, 'value': np.uint16}
+    svm_file = (('sv', 'pair_coef'), 'is an SVM model file, not a forest (vt.svm.load_model reads it)')
+    with _classify.open_model(path, 'a forest model', ForestModel.ARRAYS, dtypes, foreign=svm_file) as z:
+        if str(z['format'][()]) != FORMAT:
+            raise ValueError(f"format {str(z['format'][()])!r} is not {FORMAT!r}")
+        return ForestModel(_classify.names_of(z), z['labels'], int(z['n_features']), z['tree_offset'], z['feature'], z['threshold'],
+                           z['left'], z['right'], z['value'], float(z['fit_time']))
 
 
 # ---------------------------------------------------------------------------------------------- the GPU pass
@@ -399,8 +366,7 @@ def decide(x, model, want_votes=False):
     vittf_forest_decide call."""
     lib = _lib.require_device()
     f, nvox = x.shape
-    if f != model.n_features:
-        raise ValueError(f'the model was fitted on F = {model.n_features} features, the volume has F = {f}')
+    _classify.check_model_f(f, model)
     dev = x.device
     nodes, values, off = (torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else np.int16)).to(dev) for a in pack(model))
     labels = torch.empty((nvox,), dtype=torch.uint8, device=dev)
@@ -416,9 +382,4 @@ def predict(feat, model, return_votes=False):
     """uint8 device tensor with the voxel shape of `feat` (F, W', H', D'): the class INDEX 0..C-1 of every voxel
     (model.labels[index] is the value a label volume carries); with return_votes also the uint32 [C] + voxel shape votes,
     each at most trees x 65535."""
-    x0 = _on_device(feat)
-    x = _as_matrix(x0)
-    labels, votes = decide(x, model, return_votes)
-    shape = tuple(x0.shape[1:])
-    labels = labels.reshape(shape)
-    return (labels, votes.reshape((model.classes,) + shape)) if return_votes else labels
+    return _classify.predict_volume(feat, model, lambda x, m, vn: decide(x, m, return_votes), False)

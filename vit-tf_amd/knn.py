@@ -14,14 +14,11 @@ nearest; w_j = 1 ('uniform') or exp((sim_j - sim_1) / T) ('softmax': the common 
 weights is divided out, which changes no arg-max and cannot overflow); scores[c] = the sum of w_j over the ranks of class c in
 rank order; the label is the arg-max, the lowest class among equal scores.  scikit-learn is not imported anywhere.
 """
-import zipfile
-
 import numpy as np
 import torch
 
-from . import _lib
-from ._featvol import _as_matrix, _np, _on_device
-from .svm import round_samples, sample                               # noqa: F401  (sample: the SVM's, as it is)
+from . import _classify, _lib
+from ._classify import round_samples, sample                         # noqa: F401  (sample: the one of every classifier)
 
 FORMAT = 'vittf-knn-1'
 WEIGHTS = ('softmax', 'uniform')
@@ -64,17 +61,13 @@ class KnnModel:
         c = self.classes
         if self.weights not in WEIGHTS:
             raise ValueError(f'weights must be one of {WEIGHTS}, got {self.weights!r}')
-        if not 2 <= c <= _lib.KNN_MAX_CLASSES:
-            raise ValueError(f'classes must be in 2..{_lib.KNN_MAX_CLASSES}, got {c}')
-        if len(self.class_names) != c or np.any(np.diff(self.labels.astype(np.int64)) <= 0):
-            raise ValueError('class_names and labels must hold one entry per class, the labels ascending')
+        _classify.check_classes(self.class_names, self.labels, _lib.KNN_MAX_CLASSES)
         if self.bank.ndim != 2:
             raise ValueError(f'bank must be [S][F], got {self.bank.shape}')
         s, f = self.bank.shape
         if not 1 <= s <= _lib.KNN_MAX_BANK:
             raise ValueError(f'bank samples must number 1..{_lib.KNN_MAX_BANK}, got {s}')
-        if f % 32 or not 32 <= f <= 768:
-            raise ValueError(f'F must be a multiple of 32 in 32..768, got {f}: reduce the volume first (reduce_features.py)')
+        _classify.check_f(f, 768, ': reduce the volume first (reduce_features.py)')
         if not np.isfinite(self.bank).all():
             raise ValueError('a bank sample is not finite in fp16')
         if self.bank_class.shape != (s,) or np.any(np.diff(self.bank_class.astype(np.int64)) < 0) or self.bank_class.max() >= c:
@@ -97,22 +90,15 @@ def fit(samples, targets, k=20, temperature=0.07, weights='softmax', class_names
     ascending).  No optimisation: the samples are L2-normalised in fp64, rounded once to fp16 and sorted by class (in sample
     order inside a class).  k is clipped to n, with a printed note.  Deterministic."""
     x16 = round_samples(samples, normalize=True)
-    t = _np(targets, np.int64).reshape(-1)
     n = x16.shape[0]
-    if t.size != n:
-        raise ValueError(f'{t.size} targets for {n} samples')
-    if n and (t.min() < 0 or t.max() > 255):
-        raise ValueError('targets must be label values in 0..255')
-    values = np.unique(t)
-    names = [str(v) for v in values] if class_names is None else [str(s) for s in class_names]
-    if len(names) != values.size:
-        raise ValueError(f'{len(names)} class names for {values.size} classes')
+    values, index, names = _classify.class_table(targets, class_names, n)
+    _classify.check_names(names, values.size)
     k = int(k)
     if 1 <= n < k:
         print(f'Note: k = {k} is more than the {n} samples of the bank: using k = {n}')
         k = n
-    order = np.argsort(t, kind='stable')
-    return KnnModel(x16[order], np.searchsorted(values, t[order]), k, temperature, weights, names, values)
+    order = np.argsort(index, kind='stable')
+    return KnnModel(x16[order], index[order], k, temperature, weights, names, values)
 
 
 # ---------------------------------------------------------------------------------------------- files
@@ -127,35 +113,15 @@ def save_model(model, path):
 
 def is_knn_file(path):
     """True when `path` is an .npz that names itself a k-NN bank (the command line picks the classifier of --model by it)."""
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            return 'format' in z.files and str(z['format'][()]) == FORMAT
-    except Exception:
-        return False
+    return _classify.file_format(path) == FORMAT
 
 
 def load_model(path):
     """The KnnModel of a file save_model wrote; ValueError for anything else."""
-    try:
-        z = np.load(path, allow_pickle=False)
-    except zipfile.BadZipFile as e:
-        raise ValueError(f'{path} is not a readable .npz: {e}') from None
-    if not isinstance(z, np.lib.npyio.NpzFile):
-        raise ValueError(f'{path} is not an .npz of a k-NN bank')
-    with z:
-        if 'format' not in z.files or str(z['format'][()]) != FORMAT:
-            raise ValueError(f'{path} is not a k-NN bank file (format {FORMAT})')
-        missing = sorted(set(KnnModel.ARRAYS) - set(z.files))
-        if missing:
-            raise ValueError(f'{path} is not a k-NN bank file: it lacks {missing}')
-        try:
-            for key, dt in (('bank', np.float16), ('bank_class', np.uint8), ('labels', np.uint8)):
-                if z[key].dtype != dt:
-                    raise ValueError(f'{key} is {z[key].dtype}, not {np.dtype(dt)}')
-            return KnnModel(z['bank'], z['bank_class'], int(z['k']), float(z['temperature']), str(z['weights'][()]),
-                            [str(s) for s in z['class_names'].reshape(-1)], z['labels'])
-        except (TypeError, IndexError) as e:
-            raise ValueError(f'{path} is not a k-NN bank file: {e}') from None
+    dtypes = {'bank': np.float16, 'bank_class': np.uint8, 'labels': np.uint8}
+    with _classify.open_model(path, 'a k-NN bank', KnnModel.ARRAYS, dtypes, FORMAT) as z:
+        return KnnModel(z['bank'], z['bank_class'], int(z['k']), float(z['temperature']), str(z['weights'][()]), _classify.names_of(z),
+                        z['labels'])
 
 
 # ---------------------------------------------------------------------------------------------- the GPU pass
@@ -164,8 +130,7 @@ def decide(x, model, voxel_norm=None, want_scores=False, want_neighbours=False):
     on the device for the (F, nvox) fp16 device matrix `x`: one vittf_knn_decide call."""
     lib = _lib.require_device()
     f, nvox = x.shape
-    if f != model.n_features:
-        raise ValueError(f'the bank holds F = {model.n_features} features, the volume has F = {f}')
+    _classify.check_model_f(f, model, 'the bank holds')
     model._check()                                     # bank_class < classes: the C entry trusts it
     dev = x.device
     c, k, s = model.classes, model.k, model.n_bank
@@ -173,11 +138,7 @@ def decide(x, model, voxel_norm=None, want_scores=False, want_neighbours=False):
     scores = torch.empty((c, nvox), dtype=torch.float32, device=dev) if want_scores else None
     nn_index = torch.empty((k, nvox), dtype=torch.int32, device=dev) if want_neighbours else None
     nn_sim = torch.empty((k, nvox), dtype=torch.float32, device=dev) if want_neighbours else None
-    vn = None
-    if voxel_norm is not None:
-        vn = torch.as_tensor(voxel_norm).to(dev, torch.float32).contiguous().reshape(-1)
-        if vn.numel() != nvox:
-            raise ValueError(f'voxel_norm has {vn.numel()} entries for {nvox} voxels')
+    vn = _classify.norm_argument(voxel_norm, nvox, dev)
     with torch.cuda.device(dev):
         bank = torch.from_numpy(model.bank).to(dev)
         cls = torch.from_numpy(model.bank_class).to(dev)
@@ -195,14 +156,7 @@ def predict(feat, model, return_scores=False):
     """uint8 device tensor with the voxel shape of `feat` (F, W', H', D'): the class INDEX 0..C-1 of every voxel
     (model.labels[index] is the value a label volume carries); with return_scores also the fp32 [C] + voxel shape scores the
     arg-max was taken over.  The voxels are divided by their norms (vt.similarity.voxel_norms): the geometry is cosine."""
-    from .similarity import voxel_norms
-    x0 = _on_device(feat)
-    x = _as_matrix(x0)
-    vn = voxel_norms(x.reshape(x.shape[0], -1, 1, 1))
-    labels, scores, _, _ = decide(x, model, vn, want_scores=return_scores)
-    shape = tuple(x0.shape[1:])
-    labels = labels.reshape(shape)
-    return (labels, scores.reshape((model.classes,) + shape)) if return_scores else labels
+    return _classify.predict_volume(feat, model, lambda x, m, vn: decide(x, m, vn, want_scores=return_scores)[:2], True)
 
 
 def probabilities(scores):

@@ -22,14 +22,13 @@ model's constructor refuses (ValueError) a head whose Cauchy-Schwarz bound max_j
 through the layers from the largest norm an fp16 voxel can have, reaches 2^100.
 """
 import time
-import zipfile
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._featvol import _as_matrix, _np, _on_device
-from .svm import round_samples, sample                                                          # noqa: F401
+from . import _classify, _lib
+from ._classify import round_samples, sample                                                    # noqa: F401
+from ._featvol import _np
 
 FORMAT = 'vittf-mlp-1'
 BETAS = (0.9, 0.999)
@@ -92,12 +91,8 @@ class MlpModel:
 
     def _check(self):
         c, f, L = self.classes, self.n_features, _lib
-        if not 2 <= c <= L.MLP_MAX_CLASSES:
-            raise ValueError(f'classes must be in 2..{L.MLP_MAX_CLASSES}, got {c}')
-        if len(self.class_names) != c or np.any(np.diff(self.labels.astype(np.int64)) <= 0):
-            raise ValueError('class_names and labels must hold one entry per class, the labels ascending')
-        if f % 32 or not 32 <= f <= 1024:
-            raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
+        _classify.check_classes(self.class_names, self.labels, L.MLP_MAX_CLASSES)
+        _classify.check_f(f)
         if len(self.hidden) > L.MLP_MAX_LAYERS:
             raise ValueError(f'at most {L.MLP_MAX_LAYERS} hidden layers, got {len(self.hidden)}')
         for w in self.hidden:
@@ -115,6 +110,10 @@ class MlpModel:
         worst = max(activation_bound(self.weights, self.biases, 65504.0 * np.sqrt(f)))
         if not worst < RANGE_LIMIT:
             raise ValueError(f'the head can reach |activation| = {worst:.3g} on fp16 features: beyond 2^100 fp32 arithmetic is not safe')
+
+    def decide_slab(self, x, want_extra):
+        """(labels, the uint8 probabilities [C][n] or None) of the (F, n) matrix x, without voxel norms."""
+        return decide(x, self, None, False, want_extra)[::2]
 
 
 # ---------------------------------------------------------------------------------------------- the fit (fp64, host)
@@ -189,28 +188,18 @@ def fit(samples, targets, hidden=(), epochs=100, batch=256, lr=1e-3, weight_deca
     t0 = time.time()
     hidden = parse_hidden(hidden)
     x = round_samples(samples, normalize).astype(np.float64)
-    t = _np(targets, np.int64).reshape(-1)
     n, f = x.shape
-    if t.size != n or n < 1:
-        raise ValueError(f'{t.size} targets for {n} samples')
-    if f % 32 or not 32 <= f <= 1024:
-        raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
-    if t.min() < 0 or t.max() > 255:
-        raise ValueError('targets must be label values in 0..255')
-    values = np.unique(t)
+    if n < 1:
+        raise ValueError(f'{_np(targets, np.int64).size} targets for {n} samples')
+    values, y, names = _classify.class_table(targets, class_names, n, _lib.MLP_MAX_CLASSES, f)
     c = values.size
-    if not 2 <= c <= _lib.MLP_MAX_CLASSES:
-        raise ValueError(f'classes must be in 2..{_lib.MLP_MAX_CLASSES}, got {c}')
     if len(hidden) > _lib.MLP_MAX_LAYERS or any(w % 32 or not 32 <= w <= _lib.MLP_MAX_WIDTH for w in hidden):
         raise ValueError(f'hidden must hold at most {_lib.MLP_MAX_LAYERS} widths, multiples of 32 in 32..{_lib.MLP_MAX_WIDTH}, got {hidden}')
     if not (int(epochs) >= 1 and int(batch) >= 1):
         raise ValueError('epochs and batch must be at least 1')
     if not (lr > 0 and np.isfinite(lr) and weight_decay >= 0 and np.isfinite(weight_decay)):
         raise ValueError('lr must be positive and weight_decay not negative')
-    names = [str(v) for v in values] if class_names is None else [str(s) for s in class_names]
-    if len(names) != c:
-        raise ValueError(f'{len(names)} class names for {c} classes')
-    y = np.searchsorted(values, t)
+    _classify.check_names(names, c)
     rng = np.random.default_rng(seed)
     weights, biases = init_params((f,) + hidden + (c,), rng)
     params = [p for pair in zip(weights, biases) for p in pair]
@@ -281,43 +270,25 @@ def save_model(model, path):
 
 def is_mlp_file(path):
     """True when `path` is an .npz that names itself an MLP model (the command line picks the classifier of --model by it)."""
-    try:
-        with np.load(path, allow_pickle=False) as z:
-            return 'format' in z.files and str(z['format'][()]) == FORMAT
-    except Exception:
-        return False
+    return _classify.file_format(path) == FORMAT
 
 
 def load_model(path):
     """The MlpModel of a file save_model wrote; ValueError for anything else."""
-    try:
-        z = np.load(path, allow_pickle=False)
-    except zipfile.BadZipFile as e:
-        raise ValueError(f'{path} is not a readable .npz: {e}') from None
-    if not isinstance(z, np.lib.npyio.NpzFile):
-        raise ValueError(f'{path} is not an .npz of an MLP model')
-    with z:
-        if 'format' not in z.files or str(z['format'][()]) != FORMAT:
-            raise ValueError(f'{path} is not an MLP model file (format {FORMAT})')
-        missing = sorted(set(MlpModel.ARRAYS) - set(z.files))
-        if missing:
-            raise ValueError(f'{path} is not an MLP model file: it lacks {missing}')
-        try:
-            hidden = tuple(int(w) for w in z['hidden'].reshape(-1))
-            weights, biases = [], []
-            for i in range(len(hidden) + 1):
-                if f'weight{i}' not in z.files or f'bias{i}' not in z.files:
-                    raise ValueError(f'it lacks weight{i} / bias{i}')
-                if z[f'weight{i}'].dtype != np.float32 or z[f'bias{i}'].dtype != np.float32 or z[f'weight{i}'].ndim != 2:
-                    raise ValueError(f'weight{i} / bias{i} are not fp32 [out][in] / [out]')
-                weights.append(z[f'weight{i}'])
-                biases.append(z[f'bias{i}'])
-            if z['labels'].dtype != np.uint8:
-                raise ValueError(f"labels is {z['labels'].dtype}, not uint8")
-            return MlpModel([str(s) for s in z['class_names'].reshape(-1)], z['labels'], int(z['n_features']), bool(z['normalize']),
-                            hidden, weights, biases, float(z['fit_time']), z['loss_history'], float(z['train_accuracy']))
-        except (TypeError, IndexError) as e:
-            raise ValueError(f'{path} is not an MLP model file: {e}') from None
+    with _classify.open_model(path, 'an MLP model', MlpModel.ARRAYS, {}, FORMAT) as z:
+        hidden = tuple(int(w) for w in z['hidden'].reshape(-1))
+        weights, biases = [], []
+        for i in range(len(hidden) + 1):
+            if f'weight{i}' not in z.files or f'bias{i}' not in z.files:
+                raise ValueError(f'it lacks weight{i} / bias{i}')
+            if z[f'weight{i}'].dtype != np.float32 or z[f'bias{i}'].dtype != np.float32 or z[f'weight{i}'].ndim != 2:
+                raise ValueError(f'weight{i} / bias{i} are not fp32 [out][in] / [out]')
+            weights.append(z[f'weight{i}'])
+            biases.append(z[f'bias{i}'])
+        if z['labels'].dtype != np.uint8:
+            raise ValueError(f"labels is {z['labels'].dtype}, not uint8")
+        return MlpModel(_classify.names_of(z), z['labels'], int(z['n_features']), bool(z['normalize']), hidden, weights, biases,
+                        float(z['fit_time']), z['loss_history'], float(z['train_accuracy']))
 
 
 # ---------------------------------------------------------------------------------------------- the GPU pass
@@ -326,8 +297,7 @@ def decide(x, model, voxel_norm=None, want_logits=False, want_probs=False):
     fp16 device matrix `x`: one vittf_mlp_decide call.  probs = floor(255 softmax + 0.5) of the very logits."""
     lib = _lib.require_device()
     f, nvox = x.shape
-    if f != model.n_features:
-        raise ValueError(f'the model was fitted on F = {model.n_features} features, the volume has F = {f}')
+    _classify.check_model_f(f, model)
     dev = x.device
     c, layers = model.classes, len(model.hidden)
     labels = torch.empty((nvox,), dtype=torch.uint8, device=dev)
@@ -336,11 +306,7 @@ def decide(x, model, voxel_norm=None, want_logits=False, want_probs=False):
     w = torch.from_numpy(np.concatenate([a.reshape(-1) for a in model.weights])).to(dev)
     b = torch.from_numpy(np.concatenate(model.biases)).to(dev)
     widths = (_lib.C.c_int32 * max(layers, 1))(*model.hidden)
-    vn = None
-    if voxel_norm is not None:
-        vn = torch.as_tensor(voxel_norm).to(dev, torch.float32).contiguous().reshape(-1)
-        if vn.numel() != nvox:
-            raise ValueError(f'voxel_norm has {vn.numel()} entries for {nvox} voxels')
+    vn = _classify.norm_argument(voxel_norm, nvox, dev)
     with torch.cuda.device(dev):
         ws_bytes = lib.vittf_mlp_workspace_bytes(f, widths, layers, c)
         if ws_bytes == 0:
@@ -355,13 +321,4 @@ def predict(feat, model, return_probs=False):
     """uint8 device tensor with the voxel shape of `feat` (F, W', H', D'): the class INDEX 0..C-1 of every voxel
     (model.labels[index] is the value a label volume carries); with return_probs also the uint8 [C] + voxel shape softmax
     maps.  A model fitted with `normalize` has the voxels divided by their norms (vt.similarity.voxel_norms)."""
-    x0 = _on_device(feat)
-    x = _as_matrix(x0)
-    vn = None
-    if model.normalize:
-        from .similarity import voxel_norms
-        vn = voxel_norms(x.reshape(x.shape[0], -1, 1, 1))
-    labels, _, probs = decide(x, model, vn, False, return_probs)
-    shape = tuple(x0.shape[1:])
-    labels = labels.reshape(shape)
-    return (labels, probs.reshape((model.classes,) + shape)) if return_probs else labels
+    return _classify.predict_volume(feat, model, lambda x, m, vn: decide(x, m, vn, False, return_probs)[::2], model.normalize)

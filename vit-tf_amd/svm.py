@@ -13,13 +13,12 @@ Conventions (those of the C entries): classes are numbered 0..C-1 in ascending o
 pairs are ordered (0,1), (0,2), ..., (C-2,C-1); for the pair (i, j) a decision > 0 votes for i, anything else for j; the class
 with the most votes wins, the lowest index among equal counts.  scikit-learn is not imported anywhere.
 """
-import zipfile
-
 import numpy as np
 import torch
 
-from . import _lib
-from ._featvol import _as_matrix, _np, _on_device
+from . import _classify, _lib
+from ._classify import round_samples, sample                                                    # noqa: F401
+from ._featvol import _np
 
 KERNELS = ('rbf', 'linear')
 MAX_SAMPLES_PER_CLASS = 4096          # a pair's fp64 kernel matrix is then at most 8192^2 x 8 bytes = 512 MB
@@ -68,20 +67,20 @@ class SvmModel:
         return int(self.labels.size)
 
     @property
+    def n_features(self):
+        return int(self.sv.shape[1])
+
+    @property
     def pairs(self):
         return self.classes * (self.classes - 1) // 2
 
     def _check(self):
         c, p = self.classes, self.pairs
         s, f = self.sv.shape
-        if not 2 <= c <= _lib.SVM_MAX_CLASSES:
-            raise ValueError(f'classes must be in 2..{_lib.SVM_MAX_CLASSES}, got {c}')
-        if len(self.class_names) != c or np.any(np.diff(self.labels.astype(np.int64)) <= 0):
-            raise ValueError('class_names and labels must hold one entry per class, the labels ascending')
+        _classify.check_classes(self.class_names, self.labels, _lib.SVM_MAX_CLASSES)
         if not 1 <= s <= _lib.SVM_MAX_SV:
             raise ValueError(f'support vectors must number 1..{_lib.SVM_MAX_SV}, got {s}')
-        if f % 32 or not 32 <= f <= 1024:
-            raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
+        _classify.check_f(f)
         if self.sv_class.shape != (s,) or np.any(np.diff(self.sv_class) < 0) or self.sv_class.min() < 0 or self.sv_class.max() >= c:
             raise ValueError('sv_class must hold the class 0..C-1 of every support vector, ascending')
         if self.pair_coef.shape != (p, s) or self.intercept.shape != (p,):
@@ -92,6 +91,10 @@ class SvmModel:
             raise ValueError('the fit statistics do not fit the number of pairs / classes')
         if not (np.isfinite(self.gamma) and self.gamma >= 0 and np.isfinite(self.pair_coef).all() and np.isfinite(self.intercept).all()):
             raise ValueError('gamma, pair_coef and intercept must be finite, gamma not negative')
+
+    def decide_slab(self, x, want_extra):
+        """(labels, the fp32 decisions [P][n] or None) of the (F, n) matrix x, without voxel norms."""
+        return decide(x, self, None, want_extra)
 
 
 def pair_list(classes):
@@ -199,21 +202,6 @@ def kernel_matrix(A, B, kernel, gamma):
     return np.exp(-gamma * np.maximum(d2, 0.0))
 
 
-def round_samples(samples, normalize=False):
-    """The samples as the solver and the kernel see them: fp64 [n][F] -> (divided by max(|row|, 1e-12) when `normalize`) ->
-    rounded to fp16."""
-    x = _np(samples, np.float64)
-    if x.ndim != 2:
-        raise ValueError(f'samples must be [n][F], got {x.shape}')
-    if normalize:
-        x = x / np.maximum(np.sqrt((x * x).sum(1, keepdims=True)), 1e-12)
-    with np.errstate(over='ignore'):
-        h = x.astype(np.float16)
-    if not np.isfinite(h).all():
-        raise ValueError('a sample is not finite in fp16')
-    return h
-
-
 def fit(samples, targets, kernel='rbf', C=1.0, gamma='scale', tol=1e-3, max_iter=None, normalize=False, class_names=None):
     """SvmModel of a one-vs-one C-SVC on samples [n][F] with integer targets [n] (label values 0..255; the classes are their
     distinct values, ascending).  The samples are rounded to fp16 first (after the L2 normalisation when `normalize`, which the
@@ -223,21 +211,12 @@ def fit(samples, targets, kernel='rbf', C=1.0, gamma='scale', tol=1e-3, max_iter
         raise ValueError(f'kernel must be one of {KERNELS}, got {kernel!r}')
     x16 = round_samples(samples, normalize)
     x = x16.astype(np.float64)
-    t = _np(targets, np.int64).reshape(-1)
     n, f = x.shape
-    if t.size != n:
-        raise ValueError(f'{t.size} targets for {n} samples')
-    if f % 32 or not 32 <= f <= 1024:
-        raise ValueError(f'F must be a multiple of 32 in 32..1024, got {f}')
-    if n and (t.min() < 0 or t.max() > 255):
-        raise ValueError('targets must be label values in 0..255')
-    values = np.unique(t)
+    values, index, names = _classify.class_table(targets, class_names, n, _lib.SVM_MAX_CLASSES, f)
     c = values.size
-    if not 2 <= c <= _lib.SVM_MAX_CLASSES:
-        raise ValueError(f'classes must be in 2..{_lib.SVM_MAX_CLASSES}, got {c}')
     if not (C > 0 and np.isfinite(C)) or not tol > 0:
         raise ValueError('C and tol must be positive')
-    members = [np.flatnonzero(t == v) for v in values]
+    members = [np.flatnonzero(index == k) for k in range(c)]
     for v, m in zip(values, members):
         if m.size > MAX_SAMPLES_PER_CLASS:
             raise ValueError(f'class {v} has {m.size} samples, more than {MAX_SAMPLES_PER_CLASS}')
@@ -249,9 +228,7 @@ def fit(samples, targets, kernel='rbf', C=1.0, gamma='scale', tol=1e-3, max_iter
     gamma = float(gamma)
     if not (np.isfinite(gamma) and gamma >= 0):
         raise ValueError(f'gamma must be finite and not negative, got {gamma}')
-    names = [str(v) for v in values] if class_names is None else [str(s) for s in class_names]
-    if len(names) != c:
-        raise ValueError(f'{len(names)} class names for {c} classes')
+    _classify.check_names(names, c)
     pairs = pair_list(c)
     alphas, rhos, iters, viols = [], [], [], []
     for i, j in pairs:
@@ -342,28 +319,13 @@ def save_model(model, path):
 def load_model(path):
     """The SvmModel of a file save_model wrote; ValueError for anything else (a missing key, shapes that disagree, another
     .npz, a .npy, a damaged file)."""
-    try:
-        z = np.load(path, allow_pickle=False)
-    except zipfile.BadZipFile as e:
-        raise ValueError(f'{path} is not a readable .npz: {e}') from None
-    if not isinstance(z, np.lib.npyio.NpzFile):
-        raise ValueError(f'{path} is not an .npz of an SVM model')
-    with z:
-        missing = sorted(set(SvmModel.ARRAYS) - set(z.files))
-        if missing:
-            raise ValueError(f'{path} is not an SVM model file: it lacks {missing}')
-        try:
-            dtypes = {'sv': np.float16, 'pair_coef': np.float32, 'intercept': np.float32, 'w': np.float32, 'labels': np.uint8}
-            for k, dt in dtypes.items():
-                if z[k].dtype != dt:
-                    raise ValueError(f'{k} is {z[k].dtype}, not {np.dtype(dt)}')
-            if z['w'].ndim != 2:
-                raise ValueError(f"w is {z['w'].shape}, not [P][F]")
-            return SvmModel(str(z['kernel'][()]), float(z['gamma']), float(z['C']), bool(z['normalize']),
-                            [str(s) for s in z['class_names'].reshape(-1)], z['labels'], z['sv'], z['sv_class'], z['pair_coef'],
-                            z['intercept'], w=z['w'], n_iter=z['n_iter'], kkt_violation=z['kkt_violation'], n_support=z['n_support'])
-        except (TypeError, IndexError) as e:
-            raise ValueError(f'{path} is not an SVM model file: {e}') from None
+    dtypes = {'sv': np.float16, 'pair_coef': np.float32, 'intercept': np.float32, 'w': np.float32, 'labels': np.uint8}
+    with _classify.open_model(path, 'an SVM model', SvmModel.ARRAYS, dtypes) as z:
+        if z['w'].ndim != 2:
+            raise ValueError(f"w is {z['w'].shape}, not [P][F]")
+        return SvmModel(str(z['kernel'][()]), float(z['gamma']), float(z['C']), bool(z['normalize']), _classify.names_of(z),
+                        z['labels'], z['sv'], z['sv_class'], z['pair_coef'], z['intercept'], w=z['w'], n_iter=z['n_iter'],
+                        kkt_violation=z['kkt_violation'], n_support=z['n_support'])
 
 
 # ---------------------------------------------------------------------------------------------- the GPU pass
@@ -372,8 +334,7 @@ def decide(x, model, voxel_norm=None, want_decision=False):
     vittf_svm_rbf_decide or vittf_svm_linear_decide call."""
     lib = _lib.require_device()
     f, nvox = x.shape
-    if f != model.sv.shape[1]:
-        raise ValueError(f'the model was fitted on F = {model.sv.shape[1]} features, the volume has F = {f}')
+    _classify.check_model_f(f, model)
     if model.kernel == 'rbf' and f > 768:
         raise ValueError(f'the RBF kernel takes F <= 768, got {f}: reduce the volume first (reduce_features.py)')
     dev = x.device
@@ -381,11 +342,7 @@ def decide(x, model, voxel_norm=None, want_decision=False):
     labels = torch.empty((nvox,), dtype=torch.uint8, device=dev)
     dec = torch.empty((p, nvox), dtype=torch.float32, device=dev) if want_decision else None
     b = torch.from_numpy(model.intercept).to(dev)
-    vn = None
-    if voxel_norm is not None:
-        vn = torch.as_tensor(voxel_norm).to(dev, torch.float32).contiguous().reshape(-1)
-        if vn.numel() != nvox:
-            raise ValueError(f'voxel_norm has {vn.numel()} entries for {nvox} voxels')
+    vn = _classify.norm_argument(voxel_norm, nvox, dev)
     with torch.cuda.device(dev):
         if model.kernel == 'rbf':
             sv = torch.from_numpy(model.sv).to(dev)
@@ -409,34 +366,4 @@ def predict(feat, model, return_decision=False):
     """uint8 device tensor with the voxel shape of `feat` (F, W', H', D'): the class INDEX 0..C-1 of every voxel
     (model.labels[index] is the value a label volume carries); with return_decision also the fp32 [P] + voxel shape decisions
     the vote was taken over.  A model fitted with `normalize` has the voxels divided by their norms (vt.similarity.voxel_norms)."""
-    x0 = _on_device(feat)
-    x = _as_matrix(x0)
-    vn = None
-    if model.normalize:
-        from .similarity import voxel_norms
-        vn = voxel_norms(x.reshape(x.shape[0], -1, 1, 1))
-    labels, dec = decide(x, model, vn, return_decision)
-    shape = tuple(x0.shape[1:])
-    labels = labels.reshape(shape)
-    return (labels, dec.reshape((model.pairs,) + shape)) if return_decision else labels
-
-
-def sample(feat, annotations, volume_shape, normalize=False):
-    """(samples fp32 [n][F] device tensor, targets int64 [n] numpy): the features at the annotated voxels, sampled the way
-    compute_similarities samples its queries (trilinear, rel = (abs + 0.5) / extent * 2 - 1 in fp32, the voxel norms passed on
-    when `normalize`).  annotations: {name: (n, 3) voxel coordinates in the volume of `volume_shape`}; the target of the i-th
-    key is i."""
-    lib = _lib.require_device()
-    from .similarity import _device_features, voxel_norms
-    dev = torch.device('cuda', torch.cuda.current_device())
-    fv = _device_features(feat, dev)
-    f, n0, n1, n2 = fv.shape
-    coords = [torch.as_tensor(v).reshape(-1, 3) for v in annotations.values()]
-    targets = np.concatenate([np.full(int(c.shape[0]), i, np.int64) for i, c in enumerate(coords)])
-    ext = torch.tensor([[int(s) for s in tuple(volume_shape)[-3:]]], dtype=torch.float32)
-    rel = ((torch.cat(coords).float() + 0.5) / ext * 2.0 - 1.0).to(dev).contiguous()
-    vn = voxel_norms(fv) if normalize else None
-    out = torch.empty((rel.shape[0], f), dtype=torch.float32, device=dev)
-    _lib.check(lib.vittf_sample_features(_lib.ptr(fv), 1, f, n0, n1, n2, _lib.ptr(rel), rel.shape[0], _lib.SAMPLE_MODES['bilinear'],
-                                         _lib.ptr(vn), _lib.ptr(out), _lib.stream_ptr()), 'vittf_sample_features')
-    return out, targets
+    return _classify.predict_volume(feat, model, lambda x, m, vn: decide(x, m, vn, return_decision), model.normalize)

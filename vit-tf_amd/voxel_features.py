@@ -175,19 +175,16 @@ def slabs(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, wan
     call left (votes: vt.forest.decide's uint32 [C][n], vt.svm.decide's fp32 decisions [P][n] or vt.mlp.decide's uint8
     probabilities [C][n]; None unless want_votes).
     The ranges start at multiples of 8 and share one [32][slab] buffer.  ``classify`` is built on it."""
-    from . import forest, mlp, svm
     lib = _lib.require_device()
     _check_channels(channels)
     vol = _volume(volume)
     st = _volume_stats(vol) if stats is None else stats
     _check_stats(st, channels)
-    is_forest, is_mlp = isinstance(model, forest.ForestModel), isinstance(model, mlp.MlpModel)
-    if not is_forest and not is_mlp and not isinstance(model, svm.SvmModel):
+    if not hasattr(model, 'decide_slab'):                     # (a KnnModel has none: its geometry needs the voxel norms)
         raise ValueError(f'model must be a ForestModel, an SvmModel or an MlpModel, got {type(model).__name__}')
-    f = model.n_features if is_forest or is_mlp else model.sv.shape[1]
-    if f != 32:
-        raise ValueError(f'the model was fitted on F = {f} features, the hand-crafted features have F = 32')
-    if not is_forest and model.normalize:
+    if model.n_features != 32:
+        raise ValueError(f'the model was fitted on F = {model.n_features} features, the hand-crafted features have F = 32')
+    if model.normalize:
         raise ValueError('a model fitted with normalize is not built for the hand-crafted features')
     slab = int(slab_voxels)
     if slab < 8 or slab % 8:
@@ -204,11 +201,7 @@ def slabs(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, wan
             if n != slab:
                 x.zero_()                                           # the rows lie elsewhere in the buffer now
             _compose_into(lib, vol, st, st_dev, channels, None, start, n, x)
-            if is_mlp:
-                labels, _, votes = mlp.decide(x, model, None, False, want_votes)
-            else:
-                labels, votes = (forest.decide(x, model, want_votes) if is_forest else svm.decide(x, model, None, want_votes))
-            yield start, n, labels, votes
+            yield (start, n) + tuple(model.decide_slab(x, want_votes))
 
 
 def classify(volume, model, channels=CHANNELS, stats=None, slab_voxels=1 << 24, want_votes=False):
