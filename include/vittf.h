@@ -752,6 +752,58 @@ int vittf_edt_sq(const uint8_t* src, int32_t n0, int32_t n1, int32_t n2, int32_t
 int vittf_edt_sq_weighted(const uint8_t* src, int32_t n0, int32_t n1, int32_t n2, int32_t value, int32_t mode,
                           const double* w2_host, float* d2_out, int32_t* site_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- direct volume rendering of an intensity volume with class maps as opacity (vit-tf_amd/render.py, render_volume.py) ----
+ * The model (tests/render_data.py restates it in fp64):
+ * Coordinates.  World box [0, n_a s_a] along volume axis a, the centre of voxel i at (i + 0.5) s_a: index coordinate x_a =
+ *   p_a / s_a - 0.5.  The class maps live on their own grid (m0, m1, m2) over the same box: x_a = p_a / (n_a s_a) m_a - 0.5.
+ * Intensity.  q = rint(65535 clamp((V - vmin) / (vmax - vmin), 0, 1)) as uint16, computed in fp64 (vittf_render_prepare).  A
+ *   sample's intensity is the border-clamped trilinear value of q, clamped to the range of its eight corners (what exact
+ *   arithmetic gives anyway).
+ * Transfer function.  table: 256 entries of fp32 (r, g, b, sigma) on the device, linear between entries, read at q / 257
+ *   (65535 = 255 x 257); sigma is extinction per world unit, finite and >= 0.
+ * Classes.  0..VITTF_RENDER_MAX_CLASSES uint8 maps (C, m0, m1, m2).  value = border-clamped trilinear map value in levels
+ *   0..255 (clamped to its corners' range), omega_c = clamp((value - lo_c) / (hi_c - lo_c), 0, 1) with integers 0 <= lo_c <
+ *   hi_c <= 255, sigma_c = strength_c omega_c with colour rgb_c; class_rgbs_host holds (r, g, b, strength) per class.
+ * Coverage.  Every sigma of a sample is multiplied by the sum of the trilinear weights of its in-bounds corners of the
+ *   intensity grid: 1 inside the hull of voxel centres, 0 from half a voxel outside the box on.
+ * Rays.  Pixel (x, y) of width x height: u = 2 (x + 0.5) / width - 1, v = 1 - 2 (y + 0.5) / height, origin eye + u ox + v oy,
+ *   direction normalize(fwd + u dx + v dy); camera_host = {eye, ox, oy, fwd, dx, dy}, 18 floats in world units.  The ray
+ *   interval is the slab intersection with the box grown by half a voxel, clipped to t >= 0; samples sit on the global lattice
+ *   t_i = (i + 0.5) dt.  A ray that misses stores 0, 0, 0, 0; a zero direction component is handled without a division.
+ * Compositing, front to back with sigma = sum_k sigma_k over the table and the classes: a = 1 - exp(-sigma dt), rgb += T a
+ *   shade (sum_k sigma_k rgb_k) / max(sigma, 1e-30), A += T a, T *= 1 - a, the ray ends when T < 2^-10.  A sample with sigma
+ *   == 0 changes nothing.  rgba_out: premultiplied fp32 (height, width, 4), every pixel stored.
+ * Shading.  shade_host = {ka, kd, eps}: shade = ka + kd |g . d| / (|g| + eps), g_a = (I(x + e_a) - I(x - e_a)) / (2 s_a) from
+ *   the border-clamped trilinear intensity (in levels of q) one voxel either way with the centre sample's fractions (24 more
+ *   voxels); kd == 0 fetches none of them.  ka, kd >= 0, eps > 0.
+ * Occupancy (vittf_render_occupancy).  One byte per 8^3 brick of the intensity grid, (ceil(n0 / 8), ceil(n1 / 8), ceil(n2 /
+ *   8)), 0 = empty.  A sample belongs to the brick of clamp(floor(x_a), 0, n_a - 1) div 8.  A brick is empty when (1) every
+ *   table entry from qmin div 257 to min(255, qmax div 257 + 1) has sigma == 0, qmin and qmax over voxels 8 b_a .. min(8 b_a +
+ *   8, n_a - 1), and (2) every class has its map maximum <= lo_c over the map voxels max(0, ((8 b_a - 1) m_a) div n_a - 1)
+ *   .. min(m_a - 1, ((8 b_a + 10) m_a) div n_a + 1) per axis: a sample of the brick has p_a / s_a in [8 b_a, 8 b_a + 9); the
+ *   rule widens that by one voxel either way, far more than the rounding of the fp32 map coordinate, and takes the floor of
+ *   the map coordinate at the lower end and its upper corner at the upper end.  vittf_render with occ jumps over runs of
+ *   samples it has proved to lie in empty bricks and gives the same bytes as with occ == NULL.
+ *
+ * Every dimension of the volume and of the map grid in 2..VITTF_RENDER_MAX_DIM, fewer than 2^31 voxels each; width and height
+ * in 1..VITTF_RENDER_MAX_IMAGE; spacing finite and > 0; dt finite and > 0 and fewer than 2^22 lattice samples between a ray
+ * origin and the far side of the box; camera finite with fwd != 0; table 16-byte aligned, rgba_out 16-byte aligned, the
+ * volume of vittf_render_prepare 16-byte and q there 8-byte aligned; anything else: VITTF_ERR_INVALID_ARG without a launch.
+ * maps, lo_host, hi_host, class_rgbs_host may be NULL with classes == 0.  vittf_render_occupancy_bytes: the bricks of a
+ * volume, 0 for a shape the calls refuse.  No atomics, every output stored once: the same call gives the same bytes. */
+#define VITTF_RENDER_MAX_DIM 2048
+#define VITTF_RENDER_MAX_IMAGE 8192
+#define VITTF_RENDER_MAX_CLASSES 8
+int vittf_render_prepare(const float* volume, int64_t nvox, double vmin, double vmax, uint16_t* q, void* stream);
+size_t vittf_render_occupancy_bytes(int32_t n0, int32_t n1, int32_t n2);
+int vittf_render_occupancy(const uint16_t* q, int32_t n0, int32_t n1, int32_t n2, const float* table, const uint8_t* maps,
+                           int32_t classes, int32_t m0, int32_t m1, int32_t m2, const int32_t* lo_host, uint8_t* occ,
+                           void* stream);
+int vittf_render(const uint16_t* q, int32_t n0, int32_t n1, int32_t n2, const float* spacing_host, const float* table,
+                 const uint8_t* maps, int32_t classes, int32_t m0, int32_t m1, int32_t m2, const int32_t* lo_host,
+                 const int32_t* hi_host, const float* class_rgbs_host, const uint8_t* occ, const float* camera_host,
+                 int32_t width, int32_t height, float dt, const float* shade_host, float* rgba_out, void* stream);
+
 /* F.interpolate(mode='nearest') of a uint8 volume (n0, n1, n2) -> (o0, o1, o2): src index = min(floor(dst * (float)in /
  * out), in - 1) per dim.  equals < 0: plain resize -- the label up-sample of predict_ntf.py:217-218; equals = c in 0..255:
  * the resized class mask (src == c) as 0/1 -- evaluate_similarities.py:63 without materialising the full-size mask. */

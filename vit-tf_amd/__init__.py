@@ -9,7 +9,7 @@ from .engine import HipViT                                          # noqa: F401
 from .extract import (sizing, feature_volume, pooled_axis, k_slices, DeviceVolume, AXIS_DIMS)     # noqa: F401
 from .similarity import sample_features3d, compute_similarities, assign_labels                    # noqa: F401
 from .synthetic import synthetic_volume, ct_like_volume, shapes                                   # noqa: F401
-from . import bilateral, components, distance, forest, kmeans, knn, mlp, pca, samplers, scores, similarity, svm, voxel_features, weights                    # noqa: F401
+from . import bilateral, components, distance, forest, kmeans, knn, mlp, pca, render, samplers, scores, similarity, svm, voxel_features, weights                    # noqa: F401
 from .pca import (Basis, feature_gram, basis_from_gram, fit_basis, project, reduce_features,     # noqa: F401
                   save_basis, load_basis, rgb_volume)
 from .kmeans import Clustering, save_clustering, load_clustering                                 # noqa: F401

@@ -142,6 +142,11 @@ SIGNATURES = {
     'vittf_edt_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'vittf_edt_sq': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     'vittf_edt_sq_weighted': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _P(C.c_double), _vp, _vp, _vp, _sz, _vp]),
+    'vittf_render_prepare': (C.c_int, [_vp, _i64, C.c_double, C.c_double, _vp, _vp]),
+    'vittf_render_occupancy_bytes': (_sz, [_i32, _i32, _i32]),
+    'vittf_render_occupancy': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _P(_i32), _vp, _vp]),
+    'vittf_render': (C.c_int, [_vp, _i32, _i32, _i32, _P(C.c_float), _vp, _vp, _i32, _i32, _i32, _i32, _P(_i32), _P(_i32),
+                               _P(C.c_float), _vp, _P(C.c_float), _i32, _i32, C.c_float, _P(C.c_float), _vp, _vp]),
     'vittf_resize_nearest_u8': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     'vittf_widen_f16': (C.c_int, [_vp, _i64, _vp, _vp]),
     'vittf_bilateral_workspace_bytes': (_sz, [_i32, _i32, _i32, C.c_double, _i32]),
@@ -197,7 +202,10 @@ KNN_MAX_CLASSES = 8       # VITTF_KNN_MAX_CLASSES: classes of one bank
 KNN_MAX_BANK = 65536      # VITTF_KNN_MAX_BANK: samples of one bank
 EDT_MAX_DIM = 2048        # VITTF_EDT_MAX_DIM: the longest axis of a vittf_edt_sq volume (16-bit stack entries in LDS)
 EDT_NO_SITE = 2 ** 31 - 1  # VITTF_EDT_NO_SITE: the int32 squared distance of a volume without a site
-VOXFEAT_CHANNELS = 11   # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
+RENDER_MAX_DIM = 2048     # VITTF_RENDER_MAX_DIM: the longest axis of a rendered volume or of its class maps (2 at the least)
+RENDER_MAX_IMAGE = 8192   # VITTF_RENDER_MAX_IMAGE: the widest and the tallest image of one vittf_render call
+RENDER_MAX_CLASSES = 8    # VITTF_RENDER_MAX_CLASSES: class maps of one vittf_render call
+VOXFEAT_CHANNELS = 11  # VITTF_VOXFEAT_CHANNELS: channels of the hand-crafted voxel features (voxel_features.hip)
 KMEANS_SPANS = 128       # most voxel spans (workgroups) of vittf_kmeans_sums; beyond 128 runs a workgroup walks several
 
 
