@@ -444,7 +444,9 @@ int vittf_similarity(const uint16_t* feat, int32_t f, int32_t n0, int32_t n1, in
  * vittf_sample_features) at rel_host -- fp32 [A][3] relative coordinates in HOST memory, formed as predict_ntf.py:56 does; they
  * travel as a kernel argument, so A = class_start_host[classes] is at most VITTF_QUERY_MAX_A --, accumulates the class maps and
  * quantises + resizes them: the same bytes as vittf_sample_features + vittf_similarity, with three launches and no copy or
- * memset between the call and the first kernel.  ws: vittf_similarity_query_workspace_bytes(classes, nvox, A, f) bytes. */
+ * memset between the call and the first kernel.  ws: vittf_similarity_query_workspace_bytes(classes, nvox, A, f) bytes: the
+ * vittf_similarity_workspace_bytes(classes, nvox, A) bytes of vittf_similarity's workspace, then the sampled queries, fp32
+ * [A][F] (what vittf_sample_features would have written). */
 #define VITTF_QUERY_MAX_A 64
 size_t vittf_similarity_query_workspace_bytes(int32_t classes, int64_t nvox, int32_t annotations, int32_t f);
 int vittf_similarity_query(const uint16_t* feat, int32_t f, int32_t n0, int32_t n1, int32_t n2, const float* rel_host,

@@ -922,6 +922,42 @@ def test_similarity_query_one_call_same_bytes(gpu, monkeypatch, grid, vol_shape,
                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr()) == -1
 
 
+@pytest.mark.parametrize('normalize', [False, True])
+def test_similarity_query_samples_like_sample_features(gpu, normalize):
+    """The queries vittf_similarity_query samples -- the fp32 [A][F] block behind the vittf_similarity_workspace_bytes(classes,
+    nvox, A) bytes of its workspace -- are vittf_sample_features' trilinear values bit for bit (one device function serves
+    both kernels): coordinates on -1 and +1, beyond them (all eight corners outside the volume), on voxel centres and in
+    between, with and without the voxel norms."""
+    lib = _lib.load()
+    g = gen(345)
+    f, grid, counts = 12, (3, 4, 5), (40, 24)
+    n0, n1, n2 = grid
+    a, nvox = sum(counts), n0 * n1 * n2
+    feat = (torch.randn(f, *grid, generator=g) * 2).half().to(gpu)
+    vnorm = vt.similarity.voxel_norms(feat).contiguous() if normalize else None
+    rel = torch.rand(a, 3, generator=g) * 2.2 - 1.1
+    rel[0], rel[1], rel[2], rel[3] = torch.tensor([-1.0, -1.0, -1.0]), torch.tensor([1.0, 1.0, 1.0]), torch.tensor([-1.0, 1.0, 0.3]), torch.tensor([1.5, 1.5, 1.5])
+    rel[4], rel[5] = torch.tensor([-1.5, -1.5, -1.5]), torch.tensor([1.5, -0.2, -1.5])
+    centres = torch.stack([torch.randint(0, s, (20,), generator=g) for s in grid], 1)
+    rel[6:26] = (centres.float() + 0.5) / torch.tensor([list(grid)], dtype=torch.float32) * 2.0 - 1.0
+    rel = rel.contiguous()
+    want = torch.full((a, f), 7.0, device=gpu)
+    _lib.check(lib.vittf_sample_features(_lib.ptr(feat), 1, f, n0, n1, n2, _lib.ptr(rel.to(gpu)), a, _lib.SAMPLE_MODES['bilinear'],
+                                         _lib.ptr(vnorm), _lib.ptr(want), _lib.stream_ptr()))
+    starts = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+    offset = lib.vittf_similarity_workspace_bytes(len(counts), nvox, a)
+    ws = torch.full((lib.vittf_similarity_query_workspace_bytes(len(counts), nvox, a, f),), 0xff, dtype=torch.uint8, device=gpu)
+    assert ws.numel() >= offset + a * f * 4 and offset % 4 == 0
+    out = torch.empty((len(counts), *grid), dtype=torch.uint8, device=gpu)
+    rel_h = np.ascontiguousarray(rel.numpy())
+    _lib.check(lib.vittf_similarity_query(_lib.ptr(feat), f, n0, n1, n2, rel_h.ctypes.data_as(C.POINTER(C.c_float)),
+                                          starts.ctypes.data_as(C.POINTER(C.c_int32)), len(counts), 0, _lib.ptr(vnorm),
+                                          n0, n1, n2, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+    got = ws[offset:offset + a * f * 4].view(torch.float32).view(a, f)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert bool((want[3:6] == 0).all()) and float(want[6:26].abs().max()) > 0.1     # all corners outside: zeros
+
+
 class _ShapeOnly:
     """compute_similarities only reads volume.shape unless the bilateral solver is asked for."""
     def __init__(self, shape):

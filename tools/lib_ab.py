@@ -11,7 +11,13 @@
       score loop (PCA projection, k-means assignment): outputs AND workspaces compared byte for byte over the smallest shapes
       that reach every template and edge of the bank frame (csrc/bank_frame.h), then each library timed twice in turn on the
       shapes of tools/svm_step.py, knn_step.py and mlp_step.py (64^3 x 384, 1024 rows); exit status 1 when any comparison
-      differs"""
+      differs
+  python tools/lib_ab.py tools/micro/build/libvittf_prev.so similarity [result.json]
+      vittf_similarity, vittf_similarity_query, vittf_similarity_maps_f32 (modes 0, 1, 2) and vittf_sample_features: outputs
+      AND workspaces (0xff before the call) compared byte for byte on the shapes and switch settings of
+      tests/sim_data.GPU_CASES and on the four quantise shapes, the *_workspace_bytes functions over a grid of arguments, then
+      each library timed twice in turn on the bench's 16-query call, the 5 x 1024 call and a 3 + 2-annotation VALU call
+      (64^3 x 384 -> 256^3); exit status 1 when any comparison differs"""
 import ctypes as C
 import json
 import os
@@ -415,8 +421,186 @@ def classifiers_mode(other, out_json):
     return report(classifier_bits(libs, dev), classifier_times(libs, dev), out_json, count_by=lambda case: case.split(' ')[0])
 
 
+# ------------------------------------------------------------------------------------------------ similarity
+SIMILARITY_ENTRIES = ('vittf_similarity', 'vittf_similarity_query', 'vittf_similarity_maps_f32', 'vittf_sample_features',
+                      'vittf_similarity_workspace_bytes', 'vittf_similarity_query_workspace_bytes', 'vittf_surface_shell_workspace_bytes')
+SIM_SWITCHES = ('VITTF_SIM_MFMA', 'VITTF_SIM_MFMA_MIN', 'VITTF_SIM_MFMA_VB', 'VITTF_SIM_SPLIT', 'VITTF_SIM_QUANT16')
+# (feature grid, output shape) of the quantise kernels: x 4, x 16 along the last dim, non-integer ratios, an output row of 15
+QUANT_PAIRS = (((8, 8, 8), (32, 32, 32)), ((8, 8, 8), (8, 8, 128)), ((6, 7, 5), (30, 35, 32)), ((8, 8, 8), (8, 8, 15)))
+
+
+def set_switches(env):
+    for k in SIM_SWITCHES:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+
+
+class SimCalls:
+    """The raw similarity calls on one device; each method returns run(lib) -> [what the call wrote], outputs and workspaces
+    new tensors filled with 0xff before every call."""
+
+    def __init__(self, libs, dev):
+        self.libs, self.dev = libs, dev
+
+    def fresh(self, n, dtype=torch.uint8):
+        return torch.full((n,), 0xff, dtype=torch.uint8, device=self.dev).view(dtype)
+
+    def workspace(self, name, *args):
+        n = getattr(self.libs['tree'], name)(*args)
+        assert n and n == getattr(self.libs['other'], name)(*args), (name, args, n)
+        return n
+
+    @staticmethod
+    def starts(counts):
+        s = [0]
+        for n in counts:
+            s.append(s[-1] + n)
+        return (C.c_int32 * len(s))(*s)
+
+    def maps_f32(self, x, half, grid, q, counts, mode, vnorm):
+        f, nvox, a = x.shape[0], x.shape[1], q.shape[0]
+        nws = self.workspace('vittf_similarity_workspace_bytes', len(counts), 0, a)
+
+        def run(lib):
+            ws, out = self.fresh(nws), self.fresh(4 * (len(counts) * nvox + 1), torch.float32)
+            _lib.check(lib.vittf_similarity_maps_f32(_lib.ptr(x), int(half), f, *grid, _lib.ptr(q), self.starts(counts), len(counts), mode, 2.0,
+                                                     _lib.ptr(vnorm), _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [out, ws]
+        return run
+
+    def similarity(self, x, grid, q, counts, o, vnorm, big=0):
+        f, nvox, a = x.shape[0], x.shape[1], q.shape[0]
+        nws = self.workspace('vittf_similarity_workspace_bytes', len(counts), nvox, a)
+
+        def run(lib):
+            ws, out = self.fresh(nws), self.fresh(len(counts) * o[0] * o[1] * o[2] + 16)
+            _lib.check(lib.vittf_similarity(_lib.ptr(x), f, *grid, _lib.ptr(q), self.starts(counts), len(counts), big, _lib.ptr(vnorm), *o,
+                                            _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [out, ws]
+        return run
+
+    def query(self, x, grid, rel, counts, o, vnorm, keep=None):
+        """keep: a dict that holds the workspace and output across calls (the timings), else fresh ones per call"""
+        f, nvox, a = x.shape[0], x.shape[1], rel.shape[0]
+        nws = self.workspace('vittf_similarity_query_workspace_bytes', len(counts), nvox, a, f)
+        rel_h = (C.c_float * (3 * a))(*rel.flatten().tolist())
+        starts = self.starts(counts)
+
+        def run(lib):
+            if keep is None or 'ws' not in keep:
+                ws, out = self.fresh(nws), self.fresh(len(counts) * o[0] * o[1] * o[2] + 16)
+                if keep is not None:
+                    keep['ws'], keep['out'] = ws, out
+            else:
+                ws, out = keep['ws'], keep['out']
+            _lib.check(lib.vittf_similarity_query(_lib.ptr(x), f, *grid, rel_h, starts, len(counts), 0, _lib.ptr(vnorm), *o, _lib.ptr(out),
+                                                  _lib.ptr(ws), nws, _lib.stream_ptr()))
+            return [out, ws]
+        return run
+
+    def sample(self, x, half, grid, rel, mode, vnorm):
+        f, a = x.shape[0], rel.shape[0]
+        rel_d = rel.to(self.dev).contiguous()
+
+        def run(lib):
+            out = self.fresh(4 * (a * f + 1), torch.float32)
+            _lib.check(lib.vittf_sample_features(_lib.ptr(x), int(half), f, *grid, _lib.ptr(rel_d), a, mode, _lib.ptr(vnorm), _lib.ptr(out),
+                                                 _lib.stream_ptr()))
+            return [out]
+        return run
+
+
+def similarity_workspace_bits(libs):
+    """The three public *_workspace_bytes functions of the files this mode covers over a grid of arguments: no GPU needed."""
+    n, same = 0, True
+    for classes in (0, 1, 2, 3, 8, 32, 33, 40, 256):
+        for nvox in (0, 1, 8, 60, 693, 8640, 64 ** 3, 2 ** 31 + 5):
+            for a in (0, 1, 7, 8, 31, 32, 33, 64, 65, 1224, 5120):
+                same &= libs['tree'].vittf_similarity_workspace_bytes(classes, nvox, a) == libs['other'].vittf_similarity_workspace_bytes(classes, nvox, a)
+                for f in (0, 12, 384, 768, 4096):
+                    same &= (libs['tree'].vittf_similarity_query_workspace_bytes(classes, nvox, a, f) ==
+                             libs['other'].vittf_similarity_query_workspace_bytes(classes, nvox, a, f))
+                    n += 1
+                n += 1
+    for shape in ((0, 1, 1), (1, 1, 1), (3, 5, 16), (17, 70, 9), (512, 512, 512), (2048, 2048, 2048)):
+        same &= libs['tree'].vittf_surface_shell_workspace_bytes(*shape) == libs['other'].vittf_surface_shell_workspace_bytes(*shape)
+        n += 1
+    return {f'workspace_bytes similarity, similarity_query, surface_shell over {n} argument tuples': bool(same)}
+
+
+def similarity_bits(libs, dev):
+    """-> {case: identical}: the shapes and switch settings of tests/sim_data.GPU_CASES through every entry, then the quantise
+    pairs under the three settings of VITTF_SIM_QUANT16."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import sim_data as sd
+    calls, res = SimCalls(libs, dev), {}
+    same = lambda run: both_same(libs, run)                   # noqa: E731
+    for case in sd.GPU_CASES:
+        name = sd.case_id(case)
+        grid, counts, a = tuple(case.grid), tuple(case.counts), int(sum(case.counts))
+        d = sd.correlated(grid, counts, case.f, sd.seed_of(case), normalized=False)
+        x, q, vnorm = d.X.to(dev), d.q.to(dev), d.vnorm.to(dev)
+        rel = torch.rand(a, 3, generator=torch.Generator().manual_seed(a)) * 2.4 - 1.2
+        set_switches(case.env)
+        for vn in (None, vnorm):
+            res[f'maps_f32 mode 0 {name} voxel_norm={vn is not None} (maps, workspace)'] = same(calls.maps_f32(x, True, grid, q, counts, 0, vn))
+        res[f'maps_f32 mode 1 {name} (maps, workspace)'] = same(calls.maps_f32(x, True, grid, q, counts, 1, None))
+        res[f'maps_f32 mode 2 fp16 {name} (maps, workspace)'] = same(calls.maps_f32(x, True, grid, q, counts, 2, vnorm))
+        res[f'maps_f32 mode 2 fp32 {name} (maps, workspace)'] = same(calls.maps_f32(x.float(), False, grid, q, counts, 2, None))
+        for o in (grid, tuple(2 * s for s in grid)):
+            res[f'similarity {name} -> {o} (maps, workspace)'] = same(calls.similarity(x, grid, q, counts, o, None))
+        res[f'similarity big_a_mean {name} (maps, workspace)'] = same(calls.similarity(x, grid, q[:counts[0]], counts[:1], grid, vnorm, big=1))
+        if a <= _lib.QUERY_MAX_A:
+            for vn in (None, vnorm):
+                res[f'similarity_query {name} voxel_norm={vn is not None} (maps, workspace)'] = same(calls.query(x, grid, rel, counts, grid, vn))
+        for mode in (0, 1):
+            res[f'sample_features mode {mode} {name}'] = same(calls.sample(x, True, grid, rel, mode, vnorm)) and \
+                same(calls.sample(x.float(), False, grid, rel, mode, None))
+    for grid, o in QUANT_PAIRS:
+        counts = (3, 2)
+        d = sd.correlated(grid, counts, 64, sum(grid) + sum(o))
+        x, q = d.X.to(dev), d.q.to(dev)
+        rel = torch.rand(5, 3, generator=torch.Generator().manual_seed(sum(o))) * 2 - 1
+        for q16 in ('1', '2', '0'):
+            set_switches({'VITTF_SIM_QUANT16': q16})
+            res[f'quantize {grid} -> {o} VITTF_SIM_QUANT16={q16}: similarity, similarity_query (maps, workspace)'] = \
+                same(calls.similarity(x, grid, q, counts, o, None)) and same(calls.query(x, grid, rel, counts, o, None))
+    set_switches({})
+    return res
+
+
+def similarity_times(libs, dev):
+    """-> {shape: timed(..)}: the bench's 16-query call, BASELINE configs[4] (5 x 1024 annotations) and a VALU call, all on a
+    64^3 x 384 volume with 256^3 maps."""
+    calls, times = SimCalls(libs, dev), {}
+    f, grid, o = 384, (64, 64, 64), (256, 256, 256)
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.nn.functional.normalize(torch.randn(f, 64 ** 3, generator=g, device=dev), dim=0).half()
+    quiet = lambda run: (lambda lib: run(lib) and None)       # noqa: E731
+    for name, counts in (('similarity_query 16 annotations (matrix cores)', (16,)), ('similarity_query 3 + 2 annotations (VALU)', (3, 2))):
+        rel = torch.rand(sum(counts), 3, generator=torch.Generator().manual_seed(1)) * 2 - 1
+        times[f'{name} 64^3x{f} -> 256^3'] = timed(libs, quiet(calls.query(x, grid, rel, counts, o, None, keep={})))
+    counts = (1024,) * 5
+    q = x[:, torch.randint(0, 64 ** 3, (sum(counts),), generator=g, device=dev)].T.float().contiguous()
+    nws = calls.workspace('vittf_similarity_workspace_bytes', 5, 64 ** 3, sum(counts))
+    ws, out, starts = calls.fresh(nws), calls.fresh(5 * 256 ** 3), calls.starts(counts)
+    times[f'similarity 5 x 1024 annotations 64^3x{f} -> 256^3'] = timed(libs, lambda lib: _lib.check(lib.vittf_similarity(
+        _lib.ptr(x), f, *grid, _lib.ptr(q), starts, 5, 0, None, *o, _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream_ptr())))
+    return times
+
+
+def similarity_mode(other, out_json):
+    libs = load_both(other, SIMILARITY_ENTRIES)
+    bits = similarity_workspace_bits(libs)
+    dev = torch.device('cuda', 0)
+    bits.update(similarity_bits(libs, dev))
+    return report(bits, similarity_times(libs, dev), out_json, count_by=lambda case: case.split(' ')[0])
+
+
 def main():
     other = sys.argv[1]
+    if len(sys.argv) > 2 and sys.argv[2] == 'similarity':
+        sys.exit(similarity_mode(other, sys.argv[3] if len(sys.argv) > 3 else None))
     if len(sys.argv) > 2 and sys.argv[2] == 'attention':
         sys.exit(attention_mode(other, sys.argv[3] if len(sys.argv) > 3 else None, int(sys.argv[4]) if len(sys.argv) > 4 else 256))
     if len(sys.argv) > 2 and sys.argv[2] == 'classifiers':

@@ -11,8 +11,6 @@
 // shapes), 16 voxels per thread and a lane-replicated LDS histogram (confusion matrix).
 #include "vittf_common.h"
 
-#include <stdlib.h>
-
 namespace {
 
 // structuring element of generate_binary_structure(3, c): offsets with |d0| + |d1| + |d2| <= c; bit (d0+1)*9 + (d1+1)*3 + (d2+1)
@@ -168,8 +166,7 @@ template <bool SHELL>
 void launch_erode(const unsigned char* src, int n0, int n1, int n2, int cls, int connectivity, unsigned char* dst, hipStream_t st) {
   if (connectivity < 1) connectivity = 1;
   if (connectivity > 3) connectivity = 3;
-  static const bool wide = [] { const char* e = getenv("VITTF_ERODE_WIDE"); return !e || atoi(e) != 0; }();
-  if (wide && n2 % 8 == 0 && ((((size_t)src) | ((size_t)dst)) & 7) == 0) {
+  if (n2 % 8 == 0 && ((((size_t)src) | ((size_t)dst)) & 7) == 0) {
     const dim3 grid((unsigned)(((int64_t)n1 * (n2 / 8) + 255) / 256), n0);
     hipLaunchKernelGGL(erode8_kernel<SHELL>, grid, dim3(256), 0, st, src, n0, n1, n2, cls, connectivity, dst);
   } else {

@@ -24,18 +24,16 @@
 //     by exactly these two streams) or ONE block of 768 features (ViT-B/8 volumes: a 32-query chunk is two units, the
 //     accumulators run over both before the activation).
 #include "vittf_internal.h"
+#include "sim_route.h"
 
-#include <stdlib.h>
 #include <vector>
 
 namespace {
 
-constexpr int SM_F = 384, SM_KS = 24, SM_THREADS = 512, SM_VOX = 256;
+constexpr int SM_KS = SM_F / 16, SM_THREADS = 512;   // (SM_F features, SM_VOX voxels per tile, SM_MAXC classes by value: sim_route.h)
 constexpr int SM_PART = 6 * 4096;       // one [32 queries][384] fp16 image: six [32][64] sub-images
 constexpr int SM_CHUNK = 2 * SM_PART;   // hi + lo: 48 KB
 
-constexpr int SM_MIN_A = 8;           // fewer annotations: the VALU kernels of similarity.hip (VITTF_SIM_MFMA_MIN overrides)
-constexpr int SM_MAXC = 32;
 struct SmClasses { int n; int start[SM_MAXC + 1]; };   // n = 0: the tables are in device memory instead
 
 // padded query p (class-major, each class padded to a multiple of 32) <- source row (-1: zero row): from the class table
@@ -408,32 +406,35 @@ __global__ __launch_bounds__(SM_THREADS) void sim_mfma_few_kernel(const unsigned
 
 }  // namespace
 
+// The workspace: [query images: ku 48 KB units per 32-query chunk | source row of every padded query | first chunk of every
+// class, then the class counts] -- the two tables only with more than SM_MAXC classes.  Byte offsets.
+struct SmLayout { size_t src_row, chunk_start, counts, total; };
+static SmLayout sm_layout(size_t chunks, int ku, int32_t classes) {
+  SmLayout L;
+  L.src_row = chunks * ku * SM_CHUNK;
+  L.chunk_start = L.src_row + align256(chunks * 32 * 4);
+  L.counts = L.chunk_start + ((size_t)classes + 1) * 4;
+  L.total = L.chunk_start + align256(((size_t)classes + 1) * 8) + 256;
+  return L;
+}
+
 size_t vittf_sim_mfma_workspace_bytes(int32_t classes, int32_t annotations) {
-  // worst case: every class padded by 31 rows, 768-wide rows (two 48 KB units per chunk); + the row map, chunk table and
-  // class counts
-  const size_t chunks = ((size_t)annotations + 31 * (size_t)classes + 31) / 32;
-  return chunks * 2 * SM_CHUNK + ((chunks * 32 * 4 + 255) & ~(size_t)255) + (((size_t)classes + 1) * 8 + 255 & ~(size_t)255) + 256;
+  // worst case: every class padded by 31 rows, 768-wide rows (two units per chunk)
+  return sm_layout(((size_t)annotations + 31 * (size_t)classes + 31) / 32, 2, classes).total;
 }
 
-// does the matrix-core path take this query set?  (asked before the profiler scope is opened: an empty scope would count
-// as a launch of the class)
-static bool sm_rows_aligned(const void* feat, int64_t nvox) { return nvox % 8 == 0 && nvox >= 8 && ((uintptr_t)feat & 15) == 0; }
-
-bool vittf_sim_mfma_applies(int32_t f, int32_t classes, int32_t total_a, const void* ws, size_t ws_bytes, const void* feat,
-                            int64_t nvox) {
-  const char* e = getenv("VITTF_SIM_MFMA_MIN");   // (read per call: the tests switch it)
-  const int min_a = e ? atoi(e) : SM_MIN_A;
-  // 768-wide rows need the whole-row LDS-DMA (16-byte aligned feature rows): their strided-load form has no registers left
-  if (!(f == SM_F || (f == 2 * SM_F && sm_rows_aligned(feat, nvox)))) return false;
-  return total_a >= min_a && ws && ws_bytes >= vittf_sim_mfma_workspace_bytes(classes, total_a);
-}
-
-// fp32 class maps [classes][nvox] + per-class maxima; returns 1 when this path does not apply
-int vittf_sim_mfma_maps(const unsigned short* feat, int32_t f, int64_t nvox, const float* qf, const int32_t* class_start_host,
-                        int32_t classes, const float* voxel_norm, float* sim, unsigned* maxbits, void* ws, size_t ws_bytes,
-                        hipStream_t st) {
+// fp32 class maps [classes][nvox] + per-class maxima by the kernel `form` names (one of the SIM_MFMA_ forms: sim_route.h decided
+// that the call is this file's and that ws holds vittf_sim_mfma_workspace_bytes); cus: compute units of the current device
+int vittf_sim_mfma_maps(SimAccum form, int cus, const unsigned short* feat, int32_t f, int64_t nvox, const float* qf,
+                        const int32_t* class_start_host, int32_t classes, const float* voxel_norm, float* sim, unsigned* maxbits,
+                        void* ws, hipStream_t st) {
   const int total_a = class_start_host[classes];
-  if (!vittf_sim_mfma_applies(f, classes, total_a, ws, ws_bytes, feat, nvox)) return 1;
+  const unsigned blocks = (unsigned)((nvox + SM_VOX - 1) / SM_VOX);
+  if (form == SIM_MFMA_FEW) {
+    hipLaunchKernelGGL(sim_mfma_few_kernel, dim3(blocks < (unsigned)cus ? blocks : (unsigned)cus), dim3(SM_THREADS), 0, st, feat, nvox,
+                       qf + (size_t)class_start_host[0] * SM_F, total_a, (int)blocks, voxel_norm, sim, maxbits);
+    return vittf_check_launch();
+  }
   SmClasses cl;
   cl.n = classes <= SM_MAXC ? classes : 0;
   for (int c = 0; c <= SM_MAXC; ++c) cl.start[c] = c <= classes && cl.n ? class_start_host[c] : 0;
@@ -441,11 +442,11 @@ int vittf_sim_mfma_maps(const unsigned short* feat, int32_t f, int64_t nvox, con
   for (int c = 0; c < classes; ++c) chunks += (size_t)(class_start_host[c + 1] - class_start_host[c] + 31) / 32;
   const int padded = (int)(chunks * 32);
   const int ku = f / SM_F;
-  char* w = (char*)ws;
-  char* img = w;
-  int* src_d = (int*)(w + chunks * ku * SM_CHUNK);
-  int* chunk_d = (int*)((char*)src_d + (((size_t)padded * 4 + 255) & ~(size_t)255));
-  float* counts_d = (float*)(chunk_d + classes + 1);
+  const SmLayout L = sm_layout(chunks, ku, classes);
+  char* img = (char*)ws;
+  int* src_d = (int*)(img + L.src_row);
+  int* chunk_d = (int*)(img + L.chunk_start);
+  float* counts_d = (float*)(img + L.counts);
   std::vector<int> src_row, chunk_start;
   std::vector<float> counts;
   if (!cl.n) {   // more classes than the argument holds: the tables go through device memory
@@ -462,37 +463,14 @@ int vittf_sim_mfma_maps(const unsigned short* feat, int32_t f, int64_t nvox, con
         hipMemcpyAsync(counts_d, counts.data(), (size_t)classes * 4, hipMemcpyHostToDevice, st) != hipSuccess)
       return VITTF_ERR_LAUNCH;
   }
-  const unsigned blocks = (unsigned)((nvox + SM_VOX - 1) / SM_VOX);
-  // whole-row LDS-DMA needs 16-byte aligned rows; other volumes take the strided loads
-  const bool dma = sm_rows_aligned(feat, nvox);
-  const int cus = vittf_current_cus();        // of the CURRENT device, per call (the rank's device, not device 0)
-  if (cus <= 0) return VITTF_ERR_NO_DEVICE;
-  if (dma && ku == 1 && cl.n == 1 && chunks == 1) {   // the interactive query: one class, one chunk; the kernel prepares the queries itself
-    vittf_note_kernel(VITTF_KERNEL_SIMILARITY, "sim_mfma_few_kernel");
-    hipLaunchKernelGGL(sim_mfma_few_kernel, dim3(blocks < (unsigned)cus ? blocks : (unsigned)cus), dim3(SM_THREADS), 0, st, feat, nvox,
-                       qf + (size_t)class_start_host[0] * SM_F, total_a, (int)blocks, voxel_norm, sim, maxbits);
-    return vittf_check_launch();
-  }
   hipLaunchKernelGGL(sim_mfma_prep, dim3((padded * 48 * ku + 255) / 256), dim3(256), 0, st, qf, cl, src_d, padded, img, ku);
-  // two voxel blocks per wave (512-voxel workgroups) when that still fills the chip; VITTF_SIM_MFMA_VB=1 forces one (read per
-  // call: the tests run both)
-  const char* evb = getenv("VITTF_SIM_MFMA_VB");
-  const int vb = (ku == 2 || !dma) ? 1 : (evb ? (atoi(evb) == 1 ? 1 : 2) : ((nvox + 2 * SM_VOX - 1) / (2 * SM_VOX) >= cus ? 2 : 1));
-  const unsigned wgs = (unsigned)((nvox + (int64_t)SM_VOX * vb - 1) / ((int64_t)SM_VOX * vb));
-#define SM_LAUNCH(DMAV, KUV, VBV)                                                                                     \
-  hipLaunchKernelGGL((sim_mfma_kernel<DMAV, KUV, VBV>), dim3(wgs), dim3(SM_THREADS), 0, st, feat, nvox, img, cl, chunk_d, counts_d, \
-                     classes, (int)chunks, voxel_norm, sim, maxbits)
-  if (ku == 2) {
-    vittf_note_kernel(VITTF_KERNEL_SIMILARITY, "sim_mfma_kernel<F 768>");
-    SM_LAUNCH(true, 2, 1);
-  } else if (vb == 2) {
-    vittf_note_kernel(VITTF_KERNEL_SIMILARITY, "sim_mfma_kernel<2 voxel blocks>");
-    SM_LAUNCH(true, 1, 2);
-  } else {
-    vittf_note_kernel(VITTF_KERNEL_SIMILARITY, "sim_mfma_kernel");
-    if (dma) SM_LAUNCH(true, 1, 1); else SM_LAUNCH(false, 1, 1);
-  }
-#undef SM_LAUNCH
+  auto kernel = sim_mfma_kernel<true, 2, 1>;                         // SIM_MFMA_768
+  if (form == SIM_MFMA_VB2) kernel = sim_mfma_kernel<true, 1, 2>;
+  if (form == SIM_MFMA_DMA) kernel = sim_mfma_kernel<true, 1, 1>;
+  if (form == SIM_MFMA_STRIDED) kernel = sim_mfma_kernel<false, 1, 1>;
+  const int64_t wg_vox = (int64_t)SM_VOX * (form == SIM_MFMA_VB2 ? 2 : 1);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((nvox + wg_vox - 1) / wg_vox)), dim3(SM_THREADS), 0, st, feat, nvox, img, cl, chunk_d,
+                     counts_d, classes, (int)chunks, voxel_norm, sim, maxbits);
   if (!cl.n && hipStreamSynchronize(st) != hipSuccess) return VITTF_ERR_LAUNCH;   // the host vectors above must outlive the copies
   return vittf_check_launch();
 }

@@ -9,8 +9,7 @@
 // annotations, coalesced 4 B per lane, and the reference's A*4 B/voxel intermediate never exists.  Query vectors
 // are wave-uniform (scalar loads of a transposed [F][16] copy); all arithmetic is fp32 like the reference CPU path.
 #include "vittf_internal.h"
-
-#include <stdlib.h>
+#include "sim_route.h"
 
 namespace {
 
@@ -21,76 +20,20 @@ __device__ __forceinline__ float feat_at(const void* feat, int64_t idx) {
   else return reinterpret_cast<const float*>(feat)[idx];
 }
 
-template <bool HALF>
-__global__ __launch_bounds__(256) void sample_kernel(const void* __restrict__ feat, int f, int n0, int n1, int n2,
-                                                     const float* __restrict__ rel, int na, int mode,
-                                                     const float* __restrict__ vnorm, float* __restrict__ out) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (int64_t)na * f) return;
-  const int a = (int)(e / f), ff = (int)(e - (int64_t)a * f);
-  // rel is in volume dim order; grid_sample's x <-> last volume dim (the flip of infer.py:67)
-  const float r0 = rel[3 * a + 0], r1 = rel[3 * a + 1], r2 = rel[3 * a + 2];
-  // unnormalise, align_corners=False: ((g + 1) * size - 1) / 2
-  const float iz = ((r0 + 1.f) * (float)n0 - 1.f) / 2.f;   // along n0 ("depth" of grid_sample)
-  const float iy = ((r1 + 1.f) * (float)n1 - 1.f) / 2.f;
-  const float ix = ((r2 + 1.f) * (float)n2 - 1.f) / 2.f;   // along n2 (contiguous)
-  const int64_t plane = (int64_t)n1 * n2;
-  const int64_t fbase = (int64_t)ff * n0 * plane;
-  float res = 0.f;
-  if (mode == VITTF_SAMPLE_NEAREST) {
-    const int x = (int)rintf(ix), y = (int)rintf(iy), z = (int)rintf(iz);
-    if (x >= 0 && x < n2 && y >= 0 && y < n1 && z >= 0 && z < n0) {
-      const int64_t vox = z * plane + (int64_t)y * n2 + x;
-      res = feat_at<HALF>(feat, fbase + vox);
-      if (vnorm) res = res / vnorm[vox];           // F.normalize(feat, dim=0): v / max(|v|, eps)
-    }
-  } else {
-    const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
-    const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
-    const float wx1 = ix - fx, wy1 = iy - fy, wz1 = iz - fz;
-    const float wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy, wz0 = (fz + 1.f) - iz;
-    // corner order and weight products of the CPU grid_sampler_3d: tnw, tne, tsw, tse, bnw, bne, bsw, bse
-#pragma unroll
-    for (int cz = 0; cz < 2; ++cz)
-#pragma unroll
-      for (int cy = 0; cy < 2; ++cy)
-#pragma unroll
-        for (int cx = 0; cx < 2; ++cx) {
-          const int x = x0 + cx, y = y0 + cy, z = z0 + cz;
-          const float wgt = (cx ? wx1 : wx0) * (cy ? wy1 : wy0) * (cz ? wz1 : wz0);
-          if (x >= 0 && x < n2 && y >= 0 && y < n1 && z >= 0 && z < n0) {
-            const int64_t vox = z * plane + (int64_t)y * n2 + x;
-            float val = feat_at<HALF>(feat, fbase + vox);
-            if (vnorm) val = val / vnorm[vox];
-            res = __fadd_rn(res, __fmul_rn(val, wgt));  // unfused, like the CPU op
-          }
-        }
-  }
-  out[e] = res;
-}
+// unnormalise, align_corners=False: ((g + 1) * size - 1) / 2
+__device__ __forceinline__ float sample_pos(float r, int n) { return ((r + 1.f) * (float)n - 1.f) / 2.f; }
 
-// The interactive query's form (vittf_similarity_query): the relative coordinates arrive as a kernel argument (at most
-// VITTF_QUERY_MAX_A annotations: no host -> device copy in front of the query), the arithmetic is sample_kernel's trilinear
-// branch word for word, and the first threads zero the per-class maxima the accumulation kernels behind it add to (no memset).
-struct RelArg { float v[3 * VITTF_QUERY_MAX_A]; };
-__global__ __launch_bounds__(256) void sample_query_kernel(const unsigned short* __restrict__ feat, int f, int n0, int n1, int n2,
-                                                           RelArg rel, int na, const float* __restrict__ vnorm,
-                                                           float* __restrict__ out, unsigned* __restrict__ maxbits, int classes) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < classes) maxbits[e] = 0u;
-  if (e >= (int64_t)na * f) return;
-  const int a = (int)(e / f), ff = (int)(e - (int64_t)a * f);
-  const float r0 = rel.v[3 * a + 0], r1 = rel.v[3 * a + 1], r2 = rel.v[3 * a + 2];
-  const float iz = ((r0 + 1.f) * (float)n0 - 1.f) / 2.f;
-  const float iy = ((r1 + 1.f) * (float)n1 - 1.f) / 2.f;
-  const float ix = ((r2 + 1.f) * (float)n2 - 1.f) / 2.f;
+// Trilinear value of feature row fbase at (iz, iy, ix): corner order and weight products of the CPU grid_sampler_3d (tnw, tne,
+// tsw, tse, bnw, bne, bsw, bse), corners outside the volume count as 0.
+template <bool HALF>
+__device__ __forceinline__ float sample_trilinear(const void* feat, int64_t fbase, int n0, int n1, int n2, float iz, float iy,
+                                                  float ix, const float* __restrict__ vnorm) {
   const int64_t plane = (int64_t)n1 * n2;
-  const int64_t fbase = (int64_t)ff * n0 * plane;
-  float res = 0.f;
   const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
   const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
   const float wx1 = ix - fx, wy1 = iy - fy, wz1 = iz - fz;
   const float wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy, wz0 = (fz + 1.f) - iz;
+  float res = 0.f;
 #pragma unroll
   for (int cz = 0; cz < 2; ++cz)
 #pragma unroll
@@ -101,12 +44,54 @@ __global__ __launch_bounds__(256) void sample_query_kernel(const unsigned short*
         const float wgt = (cx ? wx1 : wx0) * (cy ? wy1 : wy0) * (cz ? wz1 : wz0);
         if (x >= 0 && x < n2 && y >= 0 && y < n1 && z >= 0 && z < n0) {
           const int64_t vox = z * plane + (int64_t)y * n2 + x;
-          float val = feat_at<true>(feat, fbase + vox);
-          if (vnorm) val = val / vnorm[vox];
-          res = __fadd_rn(res, __fmul_rn(val, wgt));
+          float val = feat_at<HALF>(feat, fbase + vox);
+          if (vnorm) val = val / vnorm[vox];           // F.normalize(feat, dim=0): v / max(|v|, eps)
+          res = __fadd_rn(res, __fmul_rn(val, wgt));  // unfused, like the CPU op
         }
       }
+  return res;
+}
+
+template <bool HALF>
+__global__ __launch_bounds__(256) void sample_kernel(const void* __restrict__ feat, int f, int n0, int n1, int n2,
+                                                     const float* __restrict__ rel, int na, int mode,
+                                                     const float* __restrict__ vnorm, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)na * f) return;
+  const int a = (int)(e / f), ff = (int)(e - (int64_t)a * f);
+  // rel is in volume dim order; grid_sample's x <-> last volume dim (the flip of infer.py:67)
+  const float iz = sample_pos(rel[3 * a + 0], n0);   // along n0 ("depth" of grid_sample)
+  const float iy = sample_pos(rel[3 * a + 1], n1);
+  const float ix = sample_pos(rel[3 * a + 2], n2);   // along n2 (contiguous)
+  const int64_t plane = (int64_t)n1 * n2;
+  const int64_t fbase = (int64_t)ff * n0 * plane;
+  float res = 0.f;
+  if (mode == VITTF_SAMPLE_NEAREST) {
+    const int x = (int)rintf(ix), y = (int)rintf(iy), z = (int)rintf(iz);
+    if (x >= 0 && x < n2 && y >= 0 && y < n1 && z >= 0 && z < n0) {
+      const int64_t vox = z * plane + (int64_t)y * n2 + x;
+      res = feat_at<HALF>(feat, fbase + vox);
+      if (vnorm) res = res / vnorm[vox];
+    }
+  } else {
+    res = sample_trilinear<HALF>(feat, fbase, n0, n1, n2, iz, iy, ix, vnorm);
+  }
   out[e] = res;
+}
+
+// The interactive query's form (vittf_similarity_query): the relative coordinates arrive as a kernel argument (at most
+// VITTF_QUERY_MAX_A annotations: no host -> device copy in front of the query), the value is sample_kernel's trilinear one,
+// and the first threads zero the per-class maxima the accumulation kernels behind it add to (no memset).
+struct RelArg { float v[3 * VITTF_QUERY_MAX_A]; };
+__global__ __launch_bounds__(256) void sample_query_kernel(const unsigned short* __restrict__ feat, int f, int n0, int n1, int n2,
+                                                           RelArg rel, int na, const float* __restrict__ vnorm,
+                                                           float* __restrict__ out, unsigned* __restrict__ maxbits, int classes) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < classes) maxbits[e] = 0u;
+  if (e >= (int64_t)na * f) return;
+  const int a = (int)(e / f), ff = (int)(e - (int64_t)a * f);
+  out[e] = sample_trilinear<true>(feat, (int64_t)ff * n0 * n1 * n2, n0, n1, n2, sample_pos(rel.v[3 * a + 0], n0),
+                                  sample_pos(rel.v[3 * a + 1], n1), sample_pos(rel.v[3 * a + 2], n2), vnorm);
 }
 
 // ---------------------------------------------------------------- per-voxel L2 norm (cosine similarity)
@@ -169,19 +154,9 @@ __global__ __launch_bounds__(256) void voxel_norm_split_kernel(const unsigned sh
 }
 
 // ---------------------------------------------------------------- similarity
-constexpr int ACH = 16;   // annotations per pass over the volume
+// (ACH annotations per pass over the volume, at most MAXC classes per pass, SimChunk: sim_route.h)
 constexpr int VPT = 2;    // voxels per thread (4-byte loads): 64^3 voxels -> 2048 waves, 8 per CU (4 per thread left the
                           // kernel latency-bound at 0.85 TB/s with one wave per SIMD)
-constexpr int MAXC = 8;   // classes handled by one pass (more classes: several launches)
-
-struct SimChunk {
-  int n_ann;          // annotations in this chunk (<= ACH)
-  int cls[ACH];       // class of each annotation, relative to c0
-  int c0, nc;         // classes [c0, c0 + nc) are touched by this chunk
-  int first[MAXC];    // chunk holds the first annotations of that class -> overwrite instead of accumulate
-  int last[MAXC];     // chunk holds the last annotations of that class  -> finalise (mean, max)
-  float count[MAXC];    // annotations of that class (fp32, exact)
-};
 
 // qf_t: [F][ACH] fp32 transposed query block for this chunk (zero padded)
 __global__ __launch_bounds__(256) void transpose_queries(const float* __restrict__ qf, int f, int a0, int n_ann,
@@ -547,10 +522,24 @@ extern "C" size_t vittf_similarity_workspace_bytes(int32_t classes, int64_t nvox
 }
 
 namespace {
-// argument checks + the chunk walk shared by the two entry points: fp32 class maps [classes][nvox] into `sim`
+// the checks the three entries share (vittf_similarity_maps_f32 has no output shape: it passes ones)
+bool similarity_args_ok(const void* feat, const void* queries, const int32_t* class_start_host, const void* out, const void* ws,
+                        int32_t f, int32_t n0, int32_t n1, int32_t n2, int32_t classes, int32_t o0, int32_t o1, int32_t o2) {
+  if (!feat || !queries || !class_start_host || !out || !ws) return false;
+  if (f <= 0 || f > 4096 || n0 <= 0 || n1 <= 0 || n2 <= 0 || classes <= 0 || o0 <= 0 || o1 <= 0 || o2 <= 0) return false;
+  return class_start_host[classes] >= 0;
+}
+
+using AccumulateKernel = void (*)(const void*, int, int64_t, const float*, SimChunk, const float*, float, float*, unsigned*);
+template <bool BIG, int ACT, bool HALF>
+AccumulateKernel accumulate_kernel(bool split) {
+  return split ? sim_accumulate_split<BIG, ACT, HALF> : sim_accumulate<BIG, ACT, HALF>;
+}
+
+// the route (sim_route.h) and the launches it names, shared by the three entries: fp32 class maps [classes][nvox] into `sim`
 // mode 0: predict_ntf (threshold / power per annotation, class mean); 1: its single-class A > 1024 variant (mean of the
 // dots first); 2: resample_topk (clamp(0, 1) ** expo per query, group mean)
-int accumulate_class_maps(const void* feat, bool half, int32_t f, int64_t nvox, const float* qf,
+int accumulate_class_maps(const SimSwitches& sw, const void* feat, bool half, int32_t f, int64_t nvox, const float* qf,
                           const int32_t* class_start_host, int32_t classes, int32_t mode, float expo,
                           const float* voxel_norm, float* sim, unsigned* maxbits, float* qf_t, void* mfma_ws,
                           size_t mfma_ws_bytes, hipStream_t st, bool maxbits_zeroed = false) {
@@ -562,98 +551,49 @@ int accumulate_class_maps(const void* feat, bool half, int32_t f, int64_t nvox, 
   if (!maxbits_zeroed && hipMemsetAsync(maxbits, 0, (size_t)classes * 4, st) != hipSuccess) return VITTF_ERR_LAUNCH;
 
   const int total_a = class_start_host[classes];
-  if (mode == 0 && half && mfma_ws_bytes) {   // many annotations, F = 384 / 768: the volume is read once (sim_mfma.hip)
-    static const bool use_mfma = [] { const char* e = getenv("VITTF_SIM_MFMA"); return !e || atoi(e) != 0; }();
-    if (use_mfma && vittf_sim_mfma_applies(f, classes, total_a, mfma_ws, mfma_ws_bytes, feat, nvox)) {   // (asked first: an empty scope would count as a launch)
-      ProfScope ps(VITTF_KERNEL_SIMILARITY, st);
-      const int rc = vittf_sim_mfma_maps((const unsigned short*)feat, f, nvox, qf, class_start_host, classes, voxel_norm, sim,
-                                         maxbits, mfma_ws, mfma_ws_bytes, st);
-      if (rc != 1) return rc;
-    }
+  const bool ws_ok = mfma_ws && mfma_ws_bytes && mfma_ws_bytes >= vittf_sim_mfma_workspace_bytes(classes, total_a);
+  // compute units of the CURRENT device, per call (the rank's device, not device 0), and only where the route reads them
+  const bool mfma = sim_mfma_takes(f, nvox, total_a, half, mode, (uintptr_t)feat, ws_ok, sw);
+  const int cus = mfma ? vittf_current_cus() : 0;
+  if (mfma && cus <= 0) return VITTF_ERR_NO_DEVICE;
+  const SimRoute route = sim_route_accumulate(f, nvox, class_start_host, classes, half, mode, (uintptr_t)feat, ws_ok, cus, sw);
+  vittf_note_kernel(VITTF_KERNEL_SIMILARITY, route.name);
+  if (mfma) {   // many annotations, F = 384 / 768: the volume is read once (sim_mfma.hip)
+    ProfScope ps(VITTF_KERNEL_SIMILARITY, st);
+    return vittf_sim_mfma_maps(route.form, cus, (const unsigned short*)feat, f, nvox, qf, class_start_host, classes, voxel_norm, sim,
+                               maxbits, mfma_ws, st);
   }
-  const int64_t threads = (nvox + VPT - 1) / VPT;
-  const unsigned blocks = (unsigned)((threads + 255) / 256);
+  const bool split = route.form == SIM_VALU_SPLIT;
+  const AccumulateKernel kernel = mode == 1 ? accumulate_kernel<true, 0, true>(split) : mode == 0 ? accumulate_kernel<false, 0, true>(split)
+                                  : half    ? accumulate_kernel<false, 1, true>(split) : accumulate_kernel<false, 1, false>(split);
+  const unsigned blocks = split ? (unsigned)((nvox / SVPT + 63) / 64) : (unsigned)(((nvox + VPT - 1) / VPT + 255) / 256);
   // walk the annotation list in chunks of ACH; a chunk may span several (at most MAXC) classes
-  int a0 = 0;
-  while (a0 < total_a) {
+  for (int a0 = 0; a0 < total_a;) {
     SimChunk ch;
-    int c_first = 0;
-    while (class_start_host[c_first + 1] <= a0) ++c_first;
-    ch.c0 = c_first;
-    int n = 0, c = c_first;
-    while (n < ACH && a0 + n < total_a) {
-      while (class_start_host[c + 1] <= a0 + n) ++c;
-      if (c - c_first >= MAXC) break;
-      ch.cls[n] = c - c_first;
-      ++n;
-    }
-    ch.n_ann = n;
-    for (int i = n; i < ACH; ++i) ch.cls[i] = -1;
-    ch.nc = ch.cls[n - 1] + 1;
-    for (int i = 0; i < MAXC; ++i) { ch.first[i] = ch.last[i] = 0; ch.count[i] = 1.f; }
-    for (int i = 0; i < ch.nc; ++i) {
-      const int cc = c_first + i;
-      ch.first[i] = class_start_host[cc] >= a0;
-      ch.last[i] = class_start_host[cc + 1] <= a0 + n;
-      ch.count[i] = (float)(class_start_host[cc + 1] - class_start_host[cc]);
-    }
+    const int n = sim_next_chunk(class_start_host, classes, a0, &ch);
     hipLaunchKernelGGL(transpose_queries, dim3((f * ACH + 255) / 256), dim3(256), 0, st, qf, f, a0, n, qf_t);
-    // split-feature kernel when the shapes allow its 8- / 16-byte loads (VITTF_SIM_SPLIT=0: always the one-wave-per-voxel-pair kernel)
-    const char* split_env = getenv("VITTF_SIM_SPLIT");   // (read per call: the tests switch it)
-    const bool use_split = !split_env || atoi(split_env) != 0;
-    const bool split = use_split && f % 4 == 0 && nvox % 4 == 0 && ((uintptr_t)feat & 15) == 0;
-    const unsigned sblocks = (unsigned)((nvox / SVPT + 63) / 64);
-#define SIM_LAUNCH(BIG, ACT, HALF)                                                                                       \
-  {                                                                                                                      \
-    if (split) hipLaunchKernelGGL((sim_accumulate_split<BIG, ACT, HALF>), dim3(sblocks), dim3(256), 0, st, feat, f, nvox, \
-                                  qf_t, ch, voxel_norm, expo, sim, maxbits);                                             \
-    else hipLaunchKernelGGL((sim_accumulate<BIG, ACT, HALF>), dim3(blocks), dim3(256), 0, st, feat, f, nvox, qf_t, ch,   \
-                            voxel_norm, expo, sim, maxbits);                                                             \
-  }
     {
-      vittf_note_kernel(VITTF_KERNEL_SIMILARITY, split ? "sim_accumulate_split" : "sim_accumulate");
       ProfScope ps(VITTF_KERNEL_SIMILARITY, st);
-      if (mode == 1) SIM_LAUNCH(true, 0, true)
-      else if (mode == 0) SIM_LAUNCH(false, 0, true)
-      else if (half) SIM_LAUNCH(false, 1, true)
-      else SIM_LAUNCH(false, 1, false)
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, feat, f, nvox, qf_t, ch, voxel_norm, expo, sim, maxbits);
     }
-#undef SIM_LAUNCH
     a0 += n;
   }
   return VITTF_OK;
 }
-}  // namespace
 
-namespace {
 // the quantise + resize launch behind the accumulation (predict_ntf.py:95-100)
-int quantize_maps(const float* sim, const unsigned* maxbits, int32_t classes, int32_t n0, int32_t n1, int32_t n2, int32_t o0,
-                  int32_t o1, int32_t o2, uint8_t* out, hipStream_t st) {
+int quantize_maps(const SimSwitches& sw, const float* sim, const unsigned* maxbits, int32_t classes, int32_t n0, int32_t n1, int32_t n2,
+                  int32_t o0, int32_t o1, int32_t o2, uint8_t* out, hipStream_t st) {
+  using QuantizeKernel = void (*)(const float*, const unsigned*, int, int, int, int, int, int, int, unsigned char*);
+  const QuantizeKernel pow2[5] = {sim_quantize16_pow2<0>, sim_quantize16_pow2<1>, sim_quantize16_pow2<2>, sim_quantize16_pow2<3>,
+                                  sim_quantize16_pow2<4>};
+  const SimQuantRoute route = sim_route_quantize(classes, n2, o0, o1, o2, (uintptr_t)sim, (uintptr_t)out, sw);
+  const bool bytes = route.form == SIM_QUANT_BYTES;
   const int64_t total_out = (int64_t)classes * o0 * o1 * o2;
-  int64_t qblocks = (total_out + 255) / 256;
-  if (qblocks > 8192) qblocks = 8192;
-  const char* q16_env = getenv("VITTF_SIM_QUANT16");   // (read per call: the tests compare the kernels; 2 = the general 16-value form)
-  const int q16 = q16_env ? atoi(q16_env) : 1;
-  if (q16 != 0 && o2 % 16 == 0 && ((uintptr_t)out & 15) == 0 && total_out / 16 < 0x7fffffff && (int64_t)classes * o0 * o1 < 0x7fffffff) {
-    qblocks = (total_out / 16 + 255) / 256;
-    if (qblocks > 16384) qblocks = 16384;
-    const int r2 = o2 % n2 == 0 ? o2 / n2 : 0;
-    const bool pow2 = q16 == 1 && (r2 == 1 || r2 == 2 || r2 == 4 || r2 == 8 || r2 == 16) && ((uintptr_t)sim & 15) == 0 && n2 % (16 / r2) == 0 &&
-                      ((int64_t)n2 * 4) % 16 == 0;
-#define SIM_Q16P(SH) hipLaunchKernelGGL((sim_quantize16_pow2<SH>), dim3((unsigned)qblocks), dim3(256), 0, st, sim, maxbits, classes, n0, n1, n2, o0, o1, o2, out)
-    if (pow2 && r2 == 1) SIM_Q16P(0);
-    else if (pow2 && r2 == 2) SIM_Q16P(1);
-    else if (pow2 && r2 == 4) SIM_Q16P(2);
-    else if (pow2 && r2 == 8) SIM_Q16P(3);
-    else if (pow2 && r2 == 16) SIM_Q16P(4);
-    else
-      hipLaunchKernelGGL(sim_quantize16, dim3((unsigned)qblocks), dim3(256), 0, st, sim, maxbits, classes, n0, n1, n2, o0, o1,
-                         o2, out);
-#undef SIM_Q16P
-  } else {
-    hipLaunchKernelGGL(sim_quantize, dim3((unsigned)qblocks), dim3(256), 0, st, sim, maxbits, classes, n0, n1, n2, o0, o1,
-                       o2, out);
-  }
+  int64_t qblocks = ((bytes ? total_out : total_out / 16) + 255) / 256;
+  if (qblocks > (bytes ? 8192 : 16384)) qblocks = bytes ? 8192 : 16384;
+  hipLaunchKernelGGL(bytes ? sim_quantize : route.form == SIM_QUANT_16 ? sim_quantize16 : pow2[route.shift], dim3((unsigned)qblocks),
+                     dim3(256), 0, st, sim, maxbits, classes, n0, n1, n2, o0, o1, o2, out);
   return vittf_check_launch();
 }
 }  // namespace
@@ -662,22 +602,20 @@ extern "C" int vittf_similarity(const uint16_t* feat, int32_t f, int32_t n0, int
                                 const int32_t* class_start_host, int32_t classes, int32_t big_a_mean,
                                 const float* voxel_norm, int32_t o0, int32_t o1, int32_t o2, uint8_t* out, void* ws,
                                 size_t ws_bytes, void* stream) {
-  if (!feat || !qf || !class_start_host || !out || !ws) return VITTF_ERR_INVALID_ARG;
-  if (f <= 0 || f > 4096 || n0 <= 0 || n1 <= 0 || n2 <= 0 || classes <= 0 || o0 <= 0 || o1 <= 0 || o2 <= 0)
-    return VITTF_ERR_INVALID_ARG;
+  if (!similarity_args_ok(feat, qf, class_start_host, out, ws, f, n0, n1, n2, classes, o0, o1, o2)) return VITTF_ERR_INVALID_ARG;
   const int64_t nvox = (int64_t)n0 * n1 * n2;
-  if (class_start_host[classes] < 0) return VITTF_ERR_INVALID_ARG;
   const SimWs L = sim_ws_layout(classes, nvox, class_start_host[classes]);
   if (ws_bytes < L.total) return VITTF_ERR_WORKSPACE;
+  const SimSwitches sw = sim_switches_from_env();
   hipStream_t st = (hipStream_t)stream;
   char* wsb = (char*)ws;
   unsigned* maxbits = (unsigned*)wsb;
   float* qf_t = (float*)(wsb + L.qf_t);
   float* sim = (float*)(wsb + L.maps);
-  const int rc = accumulate_class_maps(feat, true, f, nvox, qf, class_start_host, classes, big_a_mean ? 1 : 0, 0.f,
+  const int rc = accumulate_class_maps(sw, feat, true, f, nvox, qf, class_start_host, classes, big_a_mean ? 1 : 0, 0.f,
                                        voxel_norm, sim, maxbits, qf_t, wsb + L.mfma, L.mfma_bytes, st);
   if (rc != VITTF_OK) return rc;
-  return quantize_maps(sim, maxbits, classes, n0, n1, n2, o0, o1, o2, out, st);
+  return quantize_maps(sw, sim, maxbits, classes, n0, n1, n2, o0, o1, o2, out, st);
 }
 
 extern "C" size_t vittf_similarity_query_workspace_bytes(int32_t classes, int64_t nvox, int32_t annotations, int32_t f) {
@@ -689,14 +627,13 @@ extern "C" int vittf_similarity_query(const uint16_t* feat, int32_t f, int32_t n
                                       const int32_t* class_start_host, int32_t classes, int32_t big_a_mean,
                                       const float* voxel_norm, int32_t o0, int32_t o1, int32_t o2, uint8_t* out, void* ws,
                                       size_t ws_bytes, void* stream) {
-  if (!feat || !rel_host || !class_start_host || !out || !ws) return VITTF_ERR_INVALID_ARG;
-  if (f <= 0 || f > 4096 || n0 <= 0 || n1 <= 0 || n2 <= 0 || classes <= 0 || o0 <= 0 || o1 <= 0 || o2 <= 0)
-    return VITTF_ERR_INVALID_ARG;
+  if (!similarity_args_ok(feat, rel_host, class_start_host, out, ws, f, n0, n1, n2, classes, o0, o1, o2)) return VITTF_ERR_INVALID_ARG;
   const int a = class_start_host[classes];
   if (a <= 0 || a > VITTF_QUERY_MAX_A || classes > 256) return VITTF_ERR_INVALID_ARG;
   const int64_t nvox = (int64_t)n0 * n1 * n2;
   const SimWs L = sim_ws_layout(classes, nvox, a);
   if (ws_bytes < L.total + align256((size_t)a * f * 4)) return VITTF_ERR_WORKSPACE;
+  const SimSwitches sw = sim_switches_from_env();
   hipStream_t st = (hipStream_t)stream;
   char* wsb = (char*)ws;
   unsigned* maxbits = (unsigned*)wsb;
@@ -706,25 +643,23 @@ extern "C" int vittf_similarity_query(const uint16_t* feat, int32_t f, int32_t n
   const int64_t total = (int64_t)a * f;
   hipLaunchKernelGGL(sample_query_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, f, n0, n1, n2, rel, a,
                      voxel_norm, qf, maxbits, classes);
-  const int rc = accumulate_class_maps(feat, true, f, nvox, qf, class_start_host, classes, big_a_mean ? 1 : 0, 0.f, voxel_norm,
+  const int rc = accumulate_class_maps(sw, feat, true, f, nvox, qf, class_start_host, classes, big_a_mean ? 1 : 0, 0.f, voxel_norm,
                                        (float*)(wsb + L.maps), maxbits, (float*)(wsb + L.qf_t), wsb + L.mfma, L.mfma_bytes, st,
                                        /*maxbits_zeroed=*/true);
   if (rc != VITTF_OK) return rc;
-  return quantize_maps((const float*)(wsb + L.maps), maxbits, classes, n0, n1, n2, o0, o1, o2, out, st);
+  return quantize_maps(sw, (const float*)(wsb + L.maps), maxbits, classes, n0, n1, n2, o0, o1, o2, out, st);
 }
 
 extern "C" int vittf_similarity_maps_f32(const void* feat, int32_t feat_is_fp16, int32_t f, int32_t n0, int32_t n1,
                                          int32_t n2, const float* qf, const int32_t* class_start_host, int32_t classes,
                                          int32_t mode, float exponent, const float* voxel_norm, float* maps_out, void* ws,
                                          size_t ws_bytes, void* stream) {
-  if (!feat || !qf || !class_start_host || !maps_out || !ws) return VITTF_ERR_INVALID_ARG;
-  if (f <= 0 || f > 4096 || n0 <= 0 || n1 <= 0 || n2 <= 0 || classes <= 0) return VITTF_ERR_INVALID_ARG;
+  if (!similarity_args_ok(feat, qf, class_start_host, maps_out, ws, f, n0, n1, n2, classes, 1, 1, 1)) return VITTF_ERR_INVALID_ARG;
   const int64_t nvox = (int64_t)n0 * n1 * n2;
-  if (class_start_host[classes] < 0) return VITTF_ERR_INVALID_ARG;
   const SimWs L = sim_ws_layout(classes, 0, class_start_host[classes]);
   if (ws_bytes < L.total) return VITTF_ERR_WORKSPACE;
   char* wsb = (char*)ws;
-  const int rc = accumulate_class_maps(feat, feat_is_fp16 != 0, f, nvox, qf, class_start_host, classes, mode, exponent,
+  const int rc = accumulate_class_maps(sim_switches_from_env(), feat, feat_is_fp16 != 0, f, nvox, qf, class_start_host, classes, mode, exponent,
                                        voxel_norm, maps_out, (unsigned*)wsb, (float*)(wsb + L.qf_t), wsb + L.mfma,
                                        L.mfma_bytes, (hipStream_t)stream);
   return rc != VITTF_OK ? rc : vittf_check_launch();

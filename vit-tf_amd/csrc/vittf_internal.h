@@ -30,10 +30,9 @@ int vittf_gemm_pp_kfeat_parts(const void* a, const void* w, const float* bias, i
 int vittf_attention_pp64(const void* qkv, void* out, int32_t batch, int32_t tokens, int32_t heads, int32_t dtype,
                          hipStream_t st);
 
-// sim_mfma.hip: the matrix-core class maps of similarity.hip; vittf_sim_mfma_maps returns 1 when the path does not apply
+// sim_mfma.hip: the matrix-core class maps of similarity.hip, which decides the kernel form (sim_route.h)
+enum SimAccum : int;
 size_t vittf_sim_mfma_workspace_bytes(int32_t classes, int32_t annotations);
-bool vittf_sim_mfma_applies(int32_t f, int32_t classes, int32_t total_a, const void* ws, size_t ws_bytes, const void* feat,
-                            int64_t nvox);
-int vittf_sim_mfma_maps(const unsigned short* feat, int32_t f, int64_t nvox, const float* qf, const int32_t* class_start_host,
-                        int32_t classes, const float* voxel_norm, float* sim, unsigned* maxbits, void* ws, size_t ws_bytes,
-                        hipStream_t st);
+int vittf_sim_mfma_maps(SimAccum form, int cus, const unsigned short* feat, int32_t f, int64_t nvox, const float* qf,
+                        const int32_t* class_start_host, int32_t classes, const float* voxel_norm, float* sim, unsigned* maxbits,
+                        void* ws, hipStream_t st);
