@@ -465,7 +465,11 @@ int vittf_similarity_maps_f32(const void* feat, int32_t feat_is_fp16, int32_t f,
 
 /* Per map (nmaps maps of nvox fp32 values): the first k voxel indices, in index order, whose value is >= the k-th largest
  * value of the map -- torch.topk(s.flatten(), K).values[-1]; (s >= that).nonzero()[:K]  (infer.py:95-96).
- * idx_out int32 [nmaps][k] (device). */
+ * idx_out int32 [nmaps][k] (device).  1 <= k <= nvox and nmaps >= 1, else VITTF_ERR_INVALID_ARG.
+ * Zeros: -0.0 and +0.0 compare equal, as under the expression's >=: on a map whose k-th largest value is a zero, voxels of
+ * either sign of zero are kept, in index order (a thresholded map is mostly zeros).  +-inf order like any value.
+ * NaN is outside the contract: with a NaN in the map the expression itself returns fewer than K indices (NaN sorts above
+ * +inf in topk and compares false under >=); the kernel then still writes k indices, and which ones is unspecified. */
 int vittf_topk_voxels(const float* maps, int32_t nmaps, int64_t nvox, int32_t k, int32_t* idx_out, void* stream);
 
 /* take_most_dissimilar's distance (infer.py:118-121): dist[i] = 1 - mean_j cos(x_i, x_j) (measure 0, F.cosine_similarity

@@ -21,9 +21,14 @@ def starts_of(counts):
 
 
 # ---------------------------------------------------------------------------------------------- reference and bound
-def class_maps_ref(X, q, counts, vnorm=None):
+K_LOG = 3.71                              # v_log_f32: absolute error of log2 c in units of 2^-24 max(|log2 c|, 1); MEASURED, see below
+TINY_F32 = 2.0 ** -126                    # smallest normal fp32: what a flushed denormal argument or result can cost
+
+
+def class_maps_ref(X, q, counts, vnorm=None, mode=0, expo=0.0):
     """fp64 class maps and a bound on what an fp32 kernel may differ by: (ref, bound, edge), each [classes][nvox]; ref and
-    bound are float64, edge is bool.
+    bound are float64, edge is bool.  mode 0 (below) is predict_ntf's map, modes 1 and 2 (at the end) are the two other
+    forms vittf_similarity_maps_f32 takes; X is the fp16 volume, for mode 2 also an fp32 one.
 
     The bound is derived from the arithmetic the kernels state, entry by entry; none of its constants is fitted.
 
@@ -50,7 +55,33 @@ def class_maps_ref(X, q, counts, vnorm=None):
 
     Class mean.  The n_c non-negative activations are summed in fp32, in any order, and divided by n_c: at most
     (n_c - 1) + 1 roundings, (n_c + 2) 2^-24 sum_a a with the second-order terms.  So
-        bound[c][v] = (sum_a e_a + (n_c + 2) 2^-24 sum_a a) / n_c."""
+        bound[c][v] = (sum_a e_a + (n_c + 2) 2^-24 sum_a a) / n_c.
+
+    Mode 1 (mean of the dots first: t = (sum_a s_a) / n_c, then where(t >= 0.25, t, 0) ** 2.5; VALU kernels only, whose
+    FMA chain over an fp32 or fp16 volume has the F roundings e_s already counts).  The n_c dots are summed in fp32 in any
+    order and divided: e_t = (sum_a e_s + (n_c + 2) 2^-24 sum_a |s_a|) / n_c.  Activation and threshold are those of mode 0
+    applied once, to t with e_t; edge marks |t - 0.25| <= e_t, and no class mean follows: bound = e_a(t, e_t).
+
+    Mode 2 (resample_topk: a = clamp(s, 0, 1) ** expo per query, group mean; expo >= 1).  The kernel computes
+    c = min(max(s, 0), 1) and a = c > 0 ? exp2(expo * log2 c) : 0 with v_log_f32 and v_exp_f32.
+      Exact points, no constant: s + e_s <= 0 gives 0 on both sides; s - e_s >= 1 gives c = 1, log2 1 = 0, expo * 0 = 0,
+      exp2 0 = 1 on both sides.  e_a = 0 there.
+      Elsewhere the clamp is 1-Lipschitz and c ** expo has the increasing derivative expo c ** (expo - 1), so moving s by e_s
+      moves a by at most expo hi ** (expo - 1) e_s with hi = min(s + e_s, 1).  On the computed c (anywhere in [lo, hi],
+      lo = max(s - e_s, 2^-149)) the exponent p = expo log2 c is off by
+          dp = expo K_LOG 2^-24 lg + 2^-24 expo lg (1 + K_LOG 2^-24),     lg = max(|log2 lo|, 1):
+      v_log_f32's absolute error K_LOG 2^-24 max(|log2 c|, 1) times expo, and the one rounding of the product (expo = 1:
+      none, the term stays); 2 ** (p + dp) = 2 ** p (1 + expm1(ln 2 dp)); v_exp_f32 adds 1 ulp = 2 * 2^-24 relative, as
+      tests/svm_data.py and tests/knn_data.py assume of it; a denormal c or result may be flushed, 2^-126 absolute:
+          e_a = expo hi ** (expo - 1) e_s + hi ** expo (expm1(ln 2 dp) (1 + 2 * 2^-24) + 2 * 2^-24) + 2^-126.
+      K_LOG is the one constant that is measured, not derived: vittf_similarity_maps_f32 in mode 2 with expo = 1 on data
+      whose dots are exact (tests/refine_data.py: unit_queries; c ** 1 = c is then known exactly and the whole deviation is
+      the two instructions'), about 28000 arguments in (0, 1) from an fp32 volume and as many from an fp16 one.  Worst observed
+      (|got - c| / c - 2 * 2^-24) / (ln 2 * 2^-24 max(|log2 c|, 1)) on an MI355X: 1.8534 (at c = 1.485e-5: 0.93 ulp of
+      log2 c = -16.04; fp16 volume 1.8013; the same in both kernel forms).  K_LOG = 3.71 is twice that, because a sample
+      of the arguments was measured and not all of them.
+    The group mean is mode 0's: bound = (sum_a e_a + (n_c + 2) 2^-24 sum_a a) / n_c.  edge is all False."""
+    assert mode in (0, 1, 2) and (mode != 2 or expo >= 1.0)
     Xd = torch.as_tensor(X).double()
     qd = torch.as_tensor(q).double()
     f, nvox = Xd.shape
@@ -69,6 +100,21 @@ def class_maps_ref(X, q, counts, vnorm=None):
         if nv is not None:
             e_s = (e_s + U * (s.abs() + e_s)) / nv
             s = s / nv
+        if mode == 1:
+            e_s = ((e_s.sum(0) + (n + 2) * U * s.abs().sum(0)) / n)[None]
+            s, n = (s.sum(0) / n)[None], 1
+        elif mode == 2:
+            lo, hi = (s - e_s).clamp(2.0 ** -149, 1.0), (s + e_s).clamp(0.0, 1.0)
+            lg = lo.log2().abs().clamp_min(1.0)
+            dp = expo * K_LOG * U * lg + U * expo * lg * (1 + K_LOG * U)
+            a = s.clamp(0.0, 1.0) ** expo
+            e_a = expo * hi ** (expo - 1) * e_s + hi ** expo * (torch.expm1(np.log(2.0) * dp) * (1 + 2 * U) + 2 * U) + TINY_F32
+            e_a = torch.where((s + e_s <= 0) | (s - e_s >= 1), torch.zeros_like(s), e_a)
+            total = a.sum(0)
+            ref[c] = total / n
+            bound[c] = (e_a.sum(0) + (n + 2) * U * total) / n
+            edge[c] = False
+            continue
         a = torch.where(s >= 0.25, s, torch.zeros_like(s)) ** 2.5
         live = s + e_s >= 0.25
         near = (s - 0.25).abs() <= e_s
@@ -76,7 +122,7 @@ def class_maps_ref(X, q, counts, vnorm=None):
         e_a = e_a + near * (0.25 + e_s) ** 2.5
         total = a.sum(0)
         ref[c] = total / n
-        bound[c] = (e_a.sum(0) + (n + 2) * U * total) / n
+        bound[c] = e_a.sum(0) if mode == 1 else (e_a.sum(0) + (n + 2) * U * total) / n
         edge[c] = near.any(0)
     return ref, bound, edge
 

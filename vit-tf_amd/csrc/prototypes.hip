@@ -11,9 +11,12 @@
 
 namespace {
 
-// order-preserving map float -> uint32 (larger float <=> larger key); NaN sorts above +inf like torch.topk
+// order-preserving map float -> uint32 (larger float <=> larger key); NaN sorts above +inf like torch.topk.  -0.0 takes the
+// key of +0.0: the replaced expression compares with >=, for which the two zeros are equal (a thresholded map is mostly zeros,
+// and which of them are kept is decided by index order alone).
 __device__ __forceinline__ unsigned order_key(float v) {
-  const unsigned b = __float_as_uint(v);
+  unsigned b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 

@@ -20,14 +20,23 @@ __device__ __forceinline__ float feat_at(const void* feat, int64_t idx) {
   else return reinterpret_cast<const float*>(feat)[idx];
 }
 
-// unnormalise, align_corners=False: ((g + 1) * size - 1) / 2
-__device__ __forceinline__ float sample_pos(float r, int n) { return ((r + 1.f) * (float)n - 1.f) / 2.f; }
+// unnormalise, align_corners=False: ((g + 1) * size - 1) / 2, every operation rounded like the CPU op's: left to itself hipcc
+// contracts the product and the subtraction into one v_fma_f32 (one rounding for two), hence the pragma (see bilateral.hip,
+// sum_squares_unfused)
+__device__ __forceinline__ float sample_pos(float r, int n) {
+#pragma clang fp contract(off)
+  const float scaled = (r + 1.f) * (float)n;
+  return (scaled - 1.f) / 2.f;
+}
 
 // Trilinear value of feature row fbase at (iz, iy, ix): corner order and weight products of the CPU grid_sampler_3d (tnw, tne,
-// tsw, tse, bnw, bne, bsw, bse), corners outside the volume count as 0.
+// tsw, tse, bnw, bne, bsw, bse), corners outside the volume count as 0.  Every product is rounded before it is added,
+// res = fl(res + fl(val * wgt)): HIP's __fmul_rn / __fadd_rn are plain `*` and `+` which hipcc contracts into v_fmac_f32 once
+// inlined, so the function switches the contraction off instead.
 template <bool HALF>
 __device__ __forceinline__ float sample_trilinear(const void* feat, int64_t fbase, int n0, int n1, int n2, float iz, float iy,
                                                   float ix, const float* __restrict__ vnorm) {
+#pragma clang fp contract(off)
   const int64_t plane = (int64_t)n1 * n2;
   const float fx = floorf(ix), fy = floorf(iy), fz = floorf(iz);
   const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
@@ -46,7 +55,8 @@ __device__ __forceinline__ float sample_trilinear(const void* feat, int64_t fbas
           const int64_t vox = z * plane + (int64_t)y * n2 + x;
           float val = feat_at<HALF>(feat, fbase + vox);
           if (vnorm) val = val / vnorm[vox];           // F.normalize(feat, dim=0): v / max(|v|, eps)
-          res = __fadd_rn(res, __fmul_rn(val, wgt));  // unfused, like the CPU op
+          const float term = val * wgt;                // unfused, like the CPU op (contract(off) above)
+          res = res + term;
         }
       }
   return res;
