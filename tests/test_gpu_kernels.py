@@ -1,5 +1,6 @@
 """GPU: each libvittf kernel, called through the C ABI, against an fp64 / oracle restatement of the op it
-replaces.  Tolerances are stated per test; integer / byte / fp16-pooling work is bit-exact."""
+replaces.  Tolerances are stated per test; integer / byte / fp16-pooling work is bit-exact.
+Attention and the block tail on inputs whose result is known bit for bit: test_gpu_attention_exact.py, test_gpu_block_tail_exact.py."""
 import ctypes as C
 
 import numpy as np
